@@ -7,12 +7,20 @@ image tower (bf16, random-init weights of the real architecture: 24 layers,
 width 1024, 16 heads, patch 14, 224x224) -> fp32 L2-normalised 768-d
 embeddings -> RCCL all-gather of every rank's embeddings (the DP result
 gather).  Weak scaling: the per-GPU batch is fixed, so the global batch grows
-with N.  JPEG decode is not in the headline timed region.  After it, two side windows
-run by default: a >= 30 s steady-state window of the same step (``--seconds``,
-``steady_state``) and two end-to-end windows that include JPEG decode (``--include-decode``):
-``e2e_with_jpeg_decode`` = the framework's device JPEG path (host entropy decode + one batched GPU
-IDCT/colour launch, utils/jpeg.py) and ``e2e_with_pillow_decode`` = Pillow on the CPU pool; then
-the text tower (``texts_per_s``).
+with N.  JPEG decode is not in the headline timed region.
+
+A plain run does only what the headline needs: set-up (image tower only), ``--warmup`` steps,
+``--steps`` timed steps, the optional ``--dump-outputs DIR`` and the result line.  ``--full`` adds
+the side measurements after the headline window: a >= 30 s steady-state window of the same step
+(``--seconds``, ``steady_state``), two end-to-end windows that include JPEG decode
+(``--include-decode``): ``e2e_with_jpeg_decode`` = the framework's device JPEG path (host entropy
+decode + one batched GPU IDCT/colour launch, utils/jpeg.py) and ``e2e_with_pillow_decode`` =
+Pillow on the CPU pool; then the text tower (``--text-steps``, ``texts_per_s``).  Without
+``--full`` those keys of the result line are null.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller, the gathered
+[world * batch, embed_dim] fp32 embeddings, as ``DIR/image_embeddings.npy`` (rank 0; above 64 MB
+a fixed, seeded sample of its rows).  Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 Launch: ``python bench.py --gpus 1`` or
 ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``.
@@ -116,16 +124,27 @@ def main():
     ap.add_argument("--model", default="ViT-L-14")
     ap.add_argument("--src-size", type=int, default=256, help="synthetic decoded image side")
     ap.add_argument("--graph", action="store_true", help="capture the step in a HIP graph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline window also run the side measurements (--seconds, "
+                         "--include-decode, --text-steps); a plain run skips them all")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's gathered embeddings to DIR/image_embeddings.npy (float32; "
+                         "a fixed seeded sample of the rows above 64 MB)")
     ap.add_argument("--text-steps", type=int, default=None,
-                    help="text-tower steps timed separately for the texts/s side metric (default = --steps; 0 = skip)")
+                    help="with --full: text-tower steps timed separately for the texts/s side metric "
+                         "(default = --steps; 0 = skip)")
     ap.add_argument("--seconds", type=float, default=30.0,
-                    help="after the K-step window, run a steady-state window of at least this many seconds "
-                         "(BASELINE.md asks >= 30 s) and report it as a side metric (0 = skip)")
+                    help="with --full: after the K-step window, run a steady-state window of at least this many "
+                         "seconds (BASELINE.md asks >= 30 s) and report it as a side metric (0 = skip)")
     ap.add_argument("--include-decode", action=argparse.BooleanOptionalAction, default=True,
-                    help="side metric: end-to-end images/s with JPEG decode (CPU thread pool, libjpeg-turbo) "
-                         "+ pinned staging + H2D + tower, timed after the headline window (--no-include-decode "
-                         "skips it)")
+                    help="with --full: side metric, end-to-end images/s with JPEG decode (CPU thread pool, "
+                         "libjpeg-turbo) + pinned staging + H2D + tower, timed after the headline window "
+                         "(--no-include-decode skips it)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:       # a plain run: the headline window only
+        args.seconds, args.include_decode, args.text_steps = 0.0, False, 0
 
     local = int(os.environ.get("LOCAL_RANK", "0"))
     st = init_distributed(tp_size=1, device=torch.device("cuda", local))   # one process per GPU, RCCL
@@ -187,6 +206,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     ok = bool(torch.isfinite(gathered).all().item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result as its caller receives it (before any side window reuses the buffer)
+        import numpy as np
+
+        rows = gathered
+        cap = (64 * 10 ** 6 - 4096) // (4 * gathered.shape[1])   # rows that fit a 64 MB float32 file
+        if gathered.shape[0] > cap:                            # fixed, seeded row sample (same rows every run)
+            pick = torch.randperm(gathered.shape[0], generator=torch.Generator().manual_seed(0))[:cap]
+            rows = gathered[pick.sort().values.to(dev)]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "image_embeddings.npy"), rows.float().cpu().numpy())
     steady = None
     if args.seconds > 0:
         # steady-state window: whole steps until >= --seconds of wall clock (BASELINE.md rule)

@@ -1,10 +1,8 @@
 """JSON-schema config / manifest validation (reference lumen_config_validator.py:19-270,
 schemas/config-schema.yaml, model_info_validator.py).  ``jsonschema`` is not installed, so
-``jsonschema_lite`` is tested directly, then against the Lumen schemas and — where the
-reference tree is present — against the reference's own schema file and example configs."""
+``jsonschema_lite`` is tested directly, then against the Lumen schemas and the example configs."""
 import copy
 import glob
-import json
 import os
 from pathlib import Path
 
@@ -17,7 +15,6 @@ from lumen_amd.resources.model_info import ModelInfo, model_info_schema_errors
 from lumen_amd.resources.validator import ConfigValidator, schema_errors
 
 ROOT = Path(__file__).resolve().parents[1]
-REF = Path("/root/reference")
 EXAMPLES = sorted(glob.glob(str(ROOT / "examples/config/*.yaml")))
 
 
@@ -128,23 +125,6 @@ def test_schema_agrees_with_pydantic():
     assert n_checked > 50
 
 
-@pytest.mark.skipif(not (REF / "packages/lumen-resources/src/lumen_resources/schemas/config-schema.yaml").exists(),
-                    reason="reference tree not present")
-def test_reference_schema_and_examples():
-    """The reference's own Draft-7 schema, run by jsonschema_lite, accepts the reference's
-    example configs and ours, and agrees with our schema on them."""
-    ref_schema = SchemaValidator.from_file(REF / "packages/lumen-resources/src/lumen_resources/schemas/config-schema.yaml")
-    ref_examples = sorted(glob.glob(str(REF / "packages/*/examples/config/*.yaml")))
-    assert ref_examples
-    for p in ref_examples + EXAMPLES:
-        data = yaml.safe_load(open(p))
-        assert ref_schema.errors(data) == [], (p, ref_schema.errors(data))
-        assert schema_errors(data) == [], (p, schema_errors(data))
-    bad = _base()
-    bad["server"]["port"] = 5
-    assert ref_schema.errors(bad) and schema_errors(bad)
-
-
 def test_model_info_schema(tmp_path):
     good = {"name": "m", "version": "1.0.0", "description": "d", "model_type": "clip", "embedding_dim": 512,
             "source": {"format": "custom", "repo_id": "x/y"},
@@ -161,11 +141,6 @@ def test_model_info_schema(tmp_path):
         d = copy.deepcopy(good)
         mut(d)
         assert any(frag in e for e in model_info_schema_errors(d)), (frag, model_info_schema_errors(d))
-    ref_mi = REF / "packages/lumen-resources/docs/examples/model_info_template.json"
-    if ref_mi.exists():
-        data = json.loads(ref_mi.read_text())
-        # the template is a documentation skeleton; it must at least parse with our schema's structure
-        assert isinstance(model_info_schema_errors(data), list)
 
 
 def test_cli_schema_only(tmp_path, capsys):

@@ -101,6 +101,7 @@ def _tp_worker(rank, world, port, kind, q):
             e1 = (full[0] - ref[39]).abs().max().item()
             e2 = (torch.cat(parts2, 1)[0] - ref[40]).abs().max().item()
             q.put((e1, e2))
+        dist.barrier()      # tear down together: rank 1 does not close its pairs while rank 0 still computes
     finally:
         dist.destroy_process_group()
 

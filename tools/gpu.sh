@@ -6,7 +6,7 @@
 #   tests          pytest -m gpu (one process, 120 s per test)
 #   tsel           pytest -m gpu on $TESTS only (one process)
 #   smoke          __graft_entry__.smoke()
-#   bench          headline bench.py (defaults)
+#   bench          headline bench.py with its side windows (--full)
 #   prof_bench     rocprofv3 kernel stats of the headline bench (3 steps)
 #   gemm           tools/gemm_bench_tiles.py on the ViT-L/14 shapes ($GEMM_TILES, $GEMM_EPI)
 #   llm_tests      fp8 / LLM-op / VLM GPU tests only
@@ -66,10 +66,10 @@ for task in "$@"; do
     tsel) step tsel 600 python -u -m pytest ${TESTS:-tests/test_comm_gpu.py} -m gpu -x -v --timeout 120 \
         --timeout-method thread ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 400 python bench.py ;;
+    bench) step bench 400 python bench.py --full ;;
     prof_bench)
       step prof_bench 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_bench -o run -- \
-        python3 bench.py --steps 3 --warmup 1 --text-steps 3 ;;
+        python3 bench.py --full --steps 3 --warmup 1 --text-steps 3 ;;
     gemm)
       step gemm 500 python -u tools/gemm_bench_tiles.py --tiles="${GEMM_TILES:--1}" --epi "${GEMM_EPI:-plain}" \
         --shapes "${GEMM_SHAPES:-vit}" ;;
