@@ -20,6 +20,7 @@
 #include "attention.h"
 #include "tuning.h"
 #include "conv.h"
+#include "gemm_w4.h"
 
 namespace lumen {
 hipError_t gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, void* C,
@@ -290,13 +291,76 @@ void gemm_w8(const at::Tensor& a, const at::Tensor& w8, const at::Tensor& scale,
                                  ks > 1 ? ws.data_ptr<float>() : nullptr, cnt, ks, cur_stream()));
 }
 
+// ---------------------------------------------------------------- 4-bit group-quantised weight GEMM
+// out = epi(a @ dq(w4)^T), dq(w4)[n, k] = code * scale[n, k / G] + wmin[n, k / G]: bias -> act | SwiGLU ->
+// + residual.  w4 uint8 [N, K / 2] (low nibble = even k), params float16 [N, K / G, 2] = (scale, wmin);
+// G in {32, 128} comes from the params shape.
+static int64_t check_w4(const at::Tensor& w4, const at::Tensor& params, int64_t K, const char* op) {
+  TORCH_CHECK(w4.is_cuda() && w4.scalar_type() == at::kByte && w4.dim() == 2 && w4.stride(1) == 1 &&
+              w4.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(w4.data_ptr()) % 16 == 0, op,
+              ": w4 must be uint8 [N, K / 2] with 16-byte aligned rows");
+  TORCH_CHECK(K == 2 * w4.size(1) && K % 32 == 0 && w4.size(0) % 16 == 0, op,
+              ": K == 2 * w4.size(1), K % 32 == 0, N % 16 == 0");
+  TORCH_CHECK(params.is_cuda() && params.scalar_type() == at::kHalf && params.dim() == 3 &&
+              params.size(0) == w4.size(0) && params.size(2) == 2 && params.size(1) > 0 && params.is_contiguous(), op,
+              ": params must be contiguous float16 [N, K / G, 2]");
+  TORCH_CHECK(K % params.size(1) == 0, op, ": params groups must divide K");
+  const int64_t G = K / params.size(1);
+  TORCH_CHECK(G == 32 || G == 128, op, ": group size must be 32 or 128");
+  return G;
+}
+
+void gemm_w4(const at::Tensor& a, const at::Tensor& w4, const at::Tensor& params, const c10::optional<at::Tensor>& bias,
+             const c10::optional<at::Tensor>& residual, int64_t act, at::Tensor out, int64_t glu) {
+  check_bf16_rows(a, "a");
+  const int64_t M = a.size(0), K = a.size(1), N = w4.size(0);
+  TORCH_CHECK(M > 0, "gemm_w4: empty a");
+  const int64_t G = check_w4(w4, params, K, "gemm_w4");
+  check_gpu(out, "out");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat, "gemm_w4: out dtype");
+  TORCH_CHECK(out.dim() == 2 && out.stride(1) == 1 && out.size(0) >= M && out.size(1) >= (glu ? N / 2 : N), "gemm_w4: out");
+  TORCH_CHECK(!glu || out.scalar_type() == at::kBFloat16, "gemm_w4: glu writes bf16");
+  lumen::GemmEpi ep{};
+  ep.alpha = 1.f;
+  ep.act = (int)act;
+  ep.glu = (int)glu;
+  ep.out_f32 = out.scalar_type() == at::kFloat;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->numel() >= N && bias->is_contiguous() &&
+                (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16), "gemm_w4: bias");
+    ep.bias = bias->data_ptr();
+    ep.bias_f32 = bias->scalar_type() == at::kFloat;
+  }
+  if (residual.has_value() && residual->defined()) {
+    check_bf16_rows(*residual, "residual");
+    ep.residual = bf(*residual);
+    ep.ldr = residual->stride(0);
+  }
+  const at::DeviceGuard guard(a.device());
+  int ks = 1;
+  at::Tensor ws;
+  uint32_t* cnt = nullptr;
+  if (M <= 32) {
+    ks = lumen::w4_dec_plan((int)M, (int)N, (int)K).ks;
+    if (ks > 1) {
+      ws = at::empty({ks, M, N}, a.options().dtype(at::kFloat));
+      cnt = splitk_counters(a, (N + 15) / 16);
+    }
+  }
+  LM_CHECK_HIP(lumen::gemm_w4(bf(a), a.stride(0), w4.data_ptr<uint8_t>(), w4.stride(0),
+                                 reinterpret_cast<const uint32_t*>(params.data_ptr()), (int)G, out.data_ptr(),
+                                 out.stride(0), (int)M, (int)N, (int)K, ep, ks > 1 ? ws.data_ptr<float>() : nullptr, cnt,
+                                 ks, cur_stream()));
+}
+
 // ---------------------------------------------------------------- decode GEMM (norm folding)
 // out = epi(rstd(a) * (a @ w^T) [* scale]) for M <= 32 rows on the skinny decode kernels.
 // norm = 1: rows are scaled by rstd = rsqrt(mean(a^2) + eps) before the bias (RMSNorm with
 // its gamma folded into w, see LLM.fold_norms), rstd from ssq_in [M, tiles] (sums of squares
 // the producing GEMM wrote) or from a itself.  ssq_out [M, N/16]: this GEMM's epilogue writes
 // the per-16-column sums of squares of its stored bf16 rows (the residual stream), for the
-// next norm-folded GEMM.  w bf16 [N, K], or float8_e4m3fn with fp32 per-row scale.
+// next norm-folded GEMM.  w bf16 [N, K], float8_e4m3fn with fp32 per-row scale, or uint8 [N, K / 2]
+// 4-bit codes whose "scale" is the float16 [N, K / G, 2] group parameter tensor (gemm_w4).
 void gemm_dec(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tensor>& scale,
               const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& residual, at::Tensor out,
               int64_t glu, int64_t norm, double eps, const c10::optional<at::Tensor>& ssq_in,
@@ -304,7 +368,9 @@ void gemm_dec(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::
   check_bf16_rows(a, "a");
   const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
   TORCH_CHECK(M > 0 && M <= 32, "gemm_dec: decode rows only (1..32)");
-  TORCH_CHECK(w.dim() == 2 && w.size(1) == K && w.stride(1) == 1 && N % 16 == 0, "gemm_dec: w [N, K], N % 16 == 0");
+  const bool is_w4 = w.scalar_type() == at::kByte;   // two 4-bit codes per byte: w [N, K / 2]
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == (is_w4 ? K / 2 : K) && w.stride(1) == 1 && N % 16 == 0,
+              "gemm_dec: w [N, K] ([N, K / 2] for 4-bit weights), N % 16 == 0");
   check_gpu(out, "out");
   TORCH_CHECK(out.dim() == 2 && out.stride(1) == 1 && out.size(0) >= M && out.size(1) >= (glu ? N / 2 : N),
               "gemm_dec: out");
@@ -344,12 +410,19 @@ void gemm_dec(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::
   }
   const at::DeviceGuard guard(a.device());
   const bool is_f8 = w.scalar_type() == at::kFloat8_e4m3fn;
-  const int ks = is_f8 ? lumen::w8_dec_plan((int)M, (int)N, (int)K).ks : lumen::skinny_ksplit((int)N, (int)K);
+  const int ks = is_w4 ? lumen::w4_dec_plan((int)M, (int)N, (int)K).ks
+                 : is_f8 ? lumen::w8_dec_plan((int)M, (int)N, (int)K).ks : lumen::skinny_ksplit((int)N, (int)K);
   at::Tensor ws;
   if (ks > 1) ws = at::empty({ks, M, N}, a.options().dtype(at::kFloat));
   uint32_t* cnt = ks > 1 ? splitk_counters(a, (N + 15) / 16) : nullptr;
   float* wsp = ks > 1 ? ws.data_ptr<float>() : nullptr;
-  if (w.scalar_type() == at::kFloat8_e4m3fn) {
+  if (is_w4) {
+    TORCH_CHECK(scale.has_value() && scale->defined(), "gemm_dec: 4-bit weights need params float16 [N, K / G, 2]");
+    const int64_t G = check_w4(w, *scale, K, "gemm_dec");
+    LM_CHECK_HIP(lumen::gemm_w4(bf(a), a.stride(0), w.data_ptr<uint8_t>(), w.stride(0),
+                                   reinterpret_cast<const uint32_t*>(scale->data_ptr()), (int)G, out.data_ptr(),
+                                   out.stride(0), (int)M, (int)N, (int)K, ep, wsp, cnt, ks, cur_stream()));
+  } else if (w.scalar_type() == at::kFloat8_e4m3fn) {
     TORCH_CHECK(scale.has_value() && scale->defined() && scale->scalar_type() == at::kFloat && scale->numel() == N,
                 "gemm_dec: fp8 weights need scale f32 [N]");
     TORCH_CHECK(K % 64 == 0 && w.stride(0) % 16 == 0, "gemm_dec: fp8 K % 64");
@@ -1039,6 +1112,8 @@ TORCH_LIBRARY(lumen, m) {
   m.def("set_tuning(int flag, int value) -> int", &set_tuning_op);
   m.def("gemm_w8(Tensor a, Tensor w8, Tensor scale, Tensor? bias, Tensor? residual, int act, Tensor(o!) out, "
         "int glu) -> ()");
+  m.def("gemm_w4(Tensor a, Tensor w4, Tensor params, Tensor? bias, Tensor? residual, int act, Tensor(o!) out, "
+        "int glu) -> ()");
   m.def("gemm_dec(Tensor a, Tensor w, Tensor? scale, Tensor? bias, Tensor? residual, Tensor(o!) out, int glu, "
         "int norm, float eps, Tensor? ssq_in, Tensor(s!)? ssq_out) -> ()");
   m.def("gemm_f8(Tensor a8, Tensor sa, Tensor w8, Tensor sw, Tensor? bias, Tensor? residual, Tensor(o!) out, "
@@ -1085,6 +1160,7 @@ TORCH_LIBRARY_IMPL(lumen, CUDA, m) {
   m.impl("gemm_probe", &gemm_probe);
   m.impl("gemm_set_dbg", &gemm_set_dbg);
   m.impl("gemm_w8", &gemm_w8);
+  m.impl("gemm_w4", &gemm_w4);
   m.impl("gemm_f8", &gemm_f8);
   m.impl("gemm_dec", &gemm_dec);
   m.impl("quant_rows_fp8", &quant_rows_fp8);

@@ -242,7 +242,8 @@ class LLM(nn.Module):
         to 1.  rms_norm(x, g) . W^T = rstd(x) * (x . W'^T), so the decode GEMMs run on the raw
         residual stream and apply rstd in their epilogue (ops.linear_dec): no norm launch and
         no normalised copy of x per token.  fp8 weights are dequantised, folded and
-        requantised per row.  Weight loads reset the flag."""
+        requantised per row, 4-bit weights per group (same group size).  Weight loads reset
+        the flag."""
         if self.norm_folded:
             return
 
@@ -252,7 +253,12 @@ class LLM(nn.Module):
             g = gamma.float()[None, :]
             for r0 in range(0, w.shape[0], 8192):            # bounded fp32 temporaries
                 blk = w[r0:r0 + 8192].float()
-                if w.dtype == torch.float8_e4m3fn:
+                if w.dtype == torch.uint8:                    # 4-bit codes: [N, K / 2] + group parameters
+                    blk = ops.dequantize_w4(w[r0:r0 + 8192], sc[r0:r0 + 8192]) * g
+                    w4, p4 = ops.quantize_w4_rows(blk, group=2 * w.shape[1] // sc.shape[1])
+                    w[r0:r0 + 8192].copy_(w4)
+                    sc[r0:r0 + 8192].copy_(p4)
+                elif w.dtype == torch.float8_e4m3fn:
                     blk = blk * sc[r0:r0 + 8192].float()[:, None] * g
                     w8, s8 = ops.quantize_fp8_rows(blk)
                     w[r0:r0 + 8192].copy_(w8)
@@ -302,6 +308,42 @@ class LLM(nn.Module):
             self.lm_head = nn.Parameter(w8, requires_grad=False)
             self.register_buffer("lm_head_s", sc, persistent=False)
         self.weight_dtype = "fp8"
+
+    @torch.no_grad()
+    def quantize_w4(self, lm_head: bool = True) -> None:
+        """4-bit decoder (weight-only): QKV / o / gate|up / down (and an untied lm_head) become
+        group-quantised 4-bit codes, uint8 [N, K / 2], with float16 (scale, wmin) per group of
+        128 (32 where the local K is no multiple of 128) in the ``<name>_s`` buffers
+        (ops.quantize_w4_rows).  Activations stay bf16 and accumulation fp32 at every row
+        count (csrc/gemm_w4.hip); the embedding stays bf16.  The RMSNorm gammas are folded
+        first (on any device) and ``norm_folded`` stays set, so the codes are never
+        requantised by a later fold."""
+        if self.weight_dtype == "w4":
+            return
+        assert self.weight_dtype == "bf16", "quantize_w4 starts from float weights"
+        self.fold_norms()
+        for l in self.layers:
+            for name in ("qkv", "o", "gu", "down"):
+                w = getattr(l, name + "_w")
+                assert w.shape[1] % 32 == 0, f"w4: local K of {name} ({w.shape[1]}) must be a multiple of 32"
+                w4, p4 = ops.quantize_w4_rows(w)
+                setattr(l, name + "_w", nn.Parameter(w4, requires_grad=False))
+                l.register_buffer(name + "_s", p4, persistent=False)
+        if lm_head and self.lm_head is not None:
+            w4, p4 = ops.quantize_w4_rows(self.lm_head)
+            self.lm_head = nn.Parameter(w4, requires_grad=False)
+            self.register_buffer("lm_head_s", p4, persistent=False)
+        self.weight_dtype = "w4"
+
+    def cache_extra(self) -> dict:
+        """What a weight shard (runtime/shard_cache.py) must record next to the tensors."""
+        return {"weight_dtype": self.weight_dtype, "norm_folded": bool(self.norm_folded)}
+
+    def apply_cache_extra(self, extra: dict) -> None:
+        """Restore :meth:`cache_extra` after the shard's tensors were loaded (a w4 shard holds folded
+        gammas: without the flag the first GPU pass would fold, and requantise, again)."""
+        self.weight_dtype = extra.get("weight_dtype", self.weight_dtype)
+        self.norm_folded = bool(extra.get("norm_folded", False))
 
     @staticmethod
     def _lin(x, l, name, bias=None, residual=None, out=None, glu=False):

@@ -196,6 +196,13 @@ class VLM(nn.Module):
             self.vision.w8a8 = True
         self.invalidate_graphs()
 
+    @torch.no_grad()
+    def quantize_w4(self) -> None:
+        """4-bit VLM: the group-quantised 4-bit decoder (LLM.quantize_w4); the vision tower and the
+        projector keep their precision."""
+        self.llm.quantize_w4()
+        self.invalidate_graphs()
+
     @property
     def device(self):
         return self.proj1_w.device

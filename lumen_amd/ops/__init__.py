@@ -105,7 +105,9 @@ def linear(
 
     ``w`` may be an OCP ``torch.float8_e4m3fn`` weight with per-output-row fp32
     ``w_scale`` [N] (weight-only fp8, :func:`quantize_fp8_rows`): the HIP kernels widen
-    it to bf16 in registers and apply the scale in the fp32 epilogue.
+    it to bf16 in registers and apply the scale in the fp32 epilogue.  A ``torch.uint8``
+    ``w`` [N, K / 2] is a 4-bit group-quantised weight (:func:`quantize_w4_rows`) whose
+    ``w_scale`` is its float16 [N, K / G, 2] parameter tensor.
 
     ``x`` is [M, K] (or [..., K]), ``w`` is [N, K].  With ``out_group`` > 0 row m is
     written to ``(m // G) * GS + RO + m % G`` of ``out`` (patch rows into a token
@@ -126,6 +128,17 @@ def linear(
     else:
         ret_shape = None
     out2 = out if out.dim() == 2 else out.view(-1, out.shape[-1])
+    if w.dtype == torch.uint8:
+        assert w_scale is not None, "4-bit weights need their group parameters (w_scale)"
+        assert table is None and out_group == 0 and alpha == 1.0, "w4 GEMM: bias / act / SwiGLU / residual epilogues"
+        assert K == 2 * w.shape[1], "w4 GEMM: x [M, K] against w4 [N, K / 2]"
+        if x.is_cuda:
+            if x2.stride(-1) != 1 or x2.stride(0) % 8 != 0:
+                x2 = x2.contiguous()
+            res2 = residual.reshape(-1, residual.shape[-1]) if residual is not None else None
+            hip_ops().gemm_w4(x2, w, w_scale, bias, res2, a, out2, int(bool(glu)))
+            return out.view(ret_shape) if ret_shape is not None else out
+        w = dequantize_w4(w, w_scale)
     if w.dtype == torch.float8_e4m3fn:
         assert w_scale is not None, "fp8 weights need w_scale"
         assert table is None and out_group == 0 and alpha == 1.0, "fp8 GEMM: bias / act / SwiGLU / residual epilogues"
@@ -172,6 +185,69 @@ def quantize_fp8_rows(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     wf = w.float()
     s = (wf.abs().amax(dim=1) / FP8_E4M3_MAX).clamp_min(1e-12)
     return (wf / s[:, None]).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn), s.contiguous()
+
+
+# ---- 4-bit group-quantised weights (weight-only, asymmetric, round to nearest per group along K)
+#   w[n, k] ~= code[n, k] * scale[n, k // G] + wmin[n, k // G],  code in 0..15
+# codes: uint8 [N, K / 2], byte j = code[2 j] | code[2 j + 1] << 4 (the MatMulNBits order; the
+# kernels of csrc/gemm_w4.hip read exactly this order, so packing permutes nothing).
+# params: float16 [N, K / G, 2] = (scale, wmin), G in {32, 128} recovered from the shape.
+W4_GROUPS = (32, 128)
+
+
+def w4_group(K: int) -> int:
+    """Group size of a [*, K] matrix: 128 when K is a multiple of 128, otherwise 32."""
+    assert K % 32 == 0, f"4-bit weights need K % 32 == 0 (K = {K})"
+    return 128 if K % 128 == 0 else 32
+
+
+def pack_w4(codes: torch.Tensor, scale: torch.Tensor, wmin: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Explicit codes [N, K] (0..15) and per-group ``scale`` / ``wmin`` [N, K / G] ->
+    (w4 uint8 [N, K / 2], params float16 [N, K / G, 2])."""
+    N, K = codes.shape
+    assert scale.shape == wmin.shape and scale.shape[0] == N and K % scale.shape[1] == 0
+    assert K // scale.shape[1] in W4_GROUPS and K % 32 == 0, "group size must be 32 or 128"
+    c = codes.to(torch.uint8)
+    assert int(c.max()) <= 15 if c.numel() else True
+    w4 = (c[:, 0::2] | (c[:, 1::2] << 4)).contiguous()
+    params = torch.stack([scale.to(torch.float16), wmin.to(torch.float16)], dim=-1).contiguous()
+    return w4, params
+
+
+def unpack_w4(w4: torch.Tensor) -> torch.Tensor:
+    """w4 uint8 [N, K / 2] -> codes uint8 [N, K] (inverse of the packing of :func:`pack_w4`)."""
+    return torch.stack([w4 & 15, w4 >> 4], dim=-1).reshape(w4.shape[0], 2 * w4.shape[1])
+
+
+def dequantize_w4(w4: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
+    """(w4, params) -> float32 [N, K]: code * scale + wmin, evaluated in fp32."""
+    N, K = w4.shape[0], 2 * w4.shape[1]
+    ng = params.shape[1]
+    assert params.shape == (N, ng, 2) and K % ng == 0 and K // ng in W4_GROUPS, "params [N, K / G, 2]"
+    p = params.float()
+    c = unpack_w4(w4).float().view(N, ng, K // ng)
+    return (c * p[:, :, 0:1] + p[:, :, 1:2]).reshape(N, K)
+
+
+def quantize_w4_rows(w: torch.Tensor, group: Optional[int] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """[N, K] weight -> (w4, params): per group of ``group`` (default :func:`w4_group`) values
+    along K, scale = (max - min) / 15 (clamped away from 0) and wmin = min, both rounded to
+    fp16 BEFORE the codes are computed, codes = round((w - wmin) / scale) in 0..15."""
+    N, K = w.shape
+    G = group or w4_group(K)
+    assert G in W4_GROUPS and K % G == 0, f"group {G} must be 32 or 128 and divide K = {K}"
+    w4 = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    params = torch.empty((N, K // G, 2), dtype=torch.float16, device=w.device)
+    for r0 in range(0, N, 8192):                              # bounded fp32 temporaries
+        wf = w[r0:r0 + 8192].float().view(-1, K // G, G)
+        lo, hi = wf.amin(dim=2), wf.amax(dim=2)
+        s = ((hi - lo) / 15.0).clamp(6.2e-5, 65504.0).to(torch.float16)    # >= the smallest normal fp16
+        m = lo.clamp(-65504.0, 65504.0).to(torch.float16)
+        c = torch.round((wf - m.float()[:, :, None]) / s.float()[:, :, None]).clamp_(0, 15)
+        w4b, pb = pack_w4(c.view(-1, K), s, m)
+        w4[r0:r0 + 8192].copy_(w4b)
+        params[r0:r0 + 8192].copy_(pb)
+    return w4, params
 
 
 def quant_rows_fp8(x: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -226,6 +302,8 @@ def linear_dec(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor]
       produced x) or is computed from x.
     * ``ssq_out`` ([>= M, N / 16] fp32): this GEMM (bf16 residual-stream output) writes the
       per-16-column sums of squares of its stored rows for the next norm-folded GEMM.
+
+    ``w`` uint8: 4-bit weights [N, K / 2] with ``w_scale`` = their group parameters.
 
     CPU (and M > 32): plain ``rms_norm`` (unit gamma) + :func:`linear`; ``ssq_*`` unused."""
     M, K = x.shape

@@ -45,6 +45,9 @@ from ..common import GenericResources, load_safetensors, pick_device, runtime_na
 log = logging.getLogger("lumen.vlm.backend")
 
 DEFAULT_MAX_NEW_TOKENS = 512
+# config precisions that select the native 4-bit decoder (q4fp16: the pack is imported as usual,
+# then quantised natively -- its own codes are not reused)
+W4_PRECISIONS = ("w4", "int4", "q4", "q4fp16")
 
 
 class BackendError(Exception):
@@ -324,18 +327,22 @@ class MI355XVLMBackend:
 
         fp8 = (self.resources.precision or "").lower() in ("fp8", "e4m3", "fp8_e4m3") or \
             os.environ.get("LUMEN_VLM_FP8", "0") == "1"
-        # pre-sharded cache: TP ranks / fp8 builds reload their own (sharded, quantised) tensors
+        # 4-bit decoder (weight-only, csrc/gemm_w4.hip): its own precision names, or LUMEN_VLM_W4=1
+        w4 = not fp8 and ((self.resources.precision or "").lower() in W4_PRECISIONS or
+                          os.environ.get("LUMEN_VLM_W4", "0") == "1")
+        # pre-sharded cache: TP ranks / fp8 / w4 builds reload their own (sharded, quantised) tensors
         cached = None
-        if shard_cache.enabled() and (self.tp.enabled or fp8) and self.device.type == "cuda" and \
+        if shard_cache.enabled() and (self.tp.enabled or fp8 or w4) and self.device.type == "cuda" and \
                 not self.resources.extra.get("random_init"):
             # key: the compute dtype AND the configured precision -- two non-fp8 precisions pick
             # different ONNX pack files from the same directory (find_vlm_pack)
             prec = (self.resources.precision or "default").lower().replace("/", "_")
-            cached = (shard_cache.shard_path(root, self.tp.world, self.tp.rank, f"{'fp8' if fp8 else 'bf16'}-{prec}"),
+            tag = "fp8" if fp8 else "w4" if w4 else "bf16"
+            cached = (shard_cache.shard_path(root, self.tp.world, self.tp.rank, f"{tag}-{prec}"),
                       shard_cache.source_fingerprint(root), cfg.to_dict())
         if cached is not None and shard_cache.valid(*cached):
             extra = shard_cache.load(m, cached[0], self.device)
-            m.llm.weight_dtype = extra.get("weight_dtype", m.llm.weight_dtype)
+            m.llm.apply_cache_extra(extra)
             if fp8 and cfg.vision_arch != "fastvit" and os.environ.get("LUMEN_VIT_FP8", "1") != "0":
                 m.vision.w8a8 = True      # the MX vision chain quantises its (bf16, cached) weights on first use
             log.info("VLM rank %d/%d weights from shard cache %s", self.tp.rank, self.tp.world, cached[0])
@@ -354,8 +361,10 @@ class MI355XVLMBackend:
                 raise ResourceNotFoundError(f"{self.resources.model_name}: model.safetensors / onnx pack missing")
             if fp8:
                 m.quantize_fp8()   # fp8 decoder + W8A8 ViT tower (config precision "fp8")
+            elif w4:
+                m.quantize_w4()    # every rank quantises its own shard; the vision tower keeps its precision
             if cached is not None:
-                shard_cache.save(m, cached[0], cached[1], cached[2], {"weight_dtype": m.llm.weight_dtype})
+                shard_cache.save(m, cached[0], cached[1], cached[2], m.llm.cache_extra())
         self.model = m.eval()
         if self.tp.enabled:
             from ...parallel.comm import Communicator
@@ -662,7 +671,8 @@ class MI355XVLMBackend:
         return BackendInfo(runtime=runtime_name(dev) if dev is not None else "mi355x-hip",
                            device=str(dev or self._device_preference), model_id=self.resources.model_info.name,
                            model_name=self.resources.model_info.name, version=self.resources.model_info.version,
-                           precisions=(["bf16", "fp8"] if self.model is not None and self.model.llm.weight_dtype == "fp8"
+                           precisions=(["bf16", self.model.llm.weight_dtype]
+                                       if self.model is not None and self.model.llm.weight_dtype in ("fp8", "w4")
                                        else ["bf16"]) if dev is None or dev.type == "cuda" else ["fp32"],
                            max_new_tokens=self._max_new_tokens or DEFAULT_MAX_NEW_TOKENS,
                            max_context_length=gc.max_position_embeddings, vision_image_size=vc.image_size,

@@ -46,6 +46,7 @@ def main():
     ap.add_argument("--full-decode", action="store_true", help="host decode: the JPEG at full resolution")
     ap.add_argument("--host-decode", action="store_true", help="Pillow on the host instead of the device JPEG path")
     ap.add_argument("--fp8", action="store_true", help="weight-only OCP e4m3 decoder weights (per-channel scales)")
+    ap.add_argument("--w4", action="store_true", help="weight-only 4-bit group-quantised decoder weights (fp16 scale / min)")
     ap.add_argument("--kv-fp8", action="store_true", help="OCP e4m3 paged KV cache (unit scale)")
     ap.add_argument("--gap-ms", type=float, default=0.0,
                     help="idle time between the TTFT requests (0: back to back, the next request arrives as the "
@@ -61,6 +62,8 @@ def main():
     m.random_init(0)
     if args.fp8:
         m.quantize_fp8()
+    elif args.w4:
+        m.quantize_w4()
     torch.cuda.synchronize()
     load_s = time.time() - t0
     kv = PagedKVCache(cfg.llm.num_layers, m.llm.Hkv, cfg.llm.head_dim, num_blocks=args.kv_blocks, device=dev,
@@ -181,7 +184,7 @@ def main():
            "B prefills; batch_decode_tok_s = steady-state decode while all B streams run",
            "prompt_tokens": len(full),
            "image_tokens": cfg.num_image_tokens, "max_new_tokens": args.max_new, "batch_max_new_tokens": args.batch_max_new, "n": args.n,
-           "preset": args.preset, "kv_cache": "fp8-e4m3" if args.kv_fp8 else "bf16", "dtype": "bf16" if not args.fp8 else "fp8-e4m3 decoder (W8A8 prefill, fp8-weight decode), " + ("W8A8 MX vision" if getattr(m.vision, "w8a8", False) else "bf16 vision"), "data": f"synthetic (random-init weights, {args.image_kind} 1024x768 JPEG, {len(jpeg) // 1024} KiB)",
+           "preset": args.preset, "kv_cache": "fp8-e4m3" if args.kv_fp8 else "bf16", "dtype": "w4 decoder (4-bit group-quantised weights, bf16 activations), bf16 vision" if args.w4 and not args.fp8 else "bf16" if not args.fp8 else "fp8-e4m3 decoder (W8A8 prefill, fp8-weight decode), " + ("W8A8 MX vision" if getattr(m.vision, "w8a8", False) else "bf16 vision"), "data": f"synthetic (random-init weights, {args.image_kind} 1024x768 JPEG, {len(jpeg) // 1024} KiB)",
            "load_s": load_s, "kv_cache_tokens": kv.capacity_tokens,
            "jpeg_decode": ("host, full resolution" if args.full_decode else
                            f"host, DCT-scaled to >= {cfg.vision.image_size}px") if args.host_decode else

@@ -1,4 +1,5 @@
-"""Decode-shaped fp8 weight GEMMs on the Llama-3-8B layer shapes, HBM-cold.
+"""Decode-shaped fp8 (or, with --w4, 4-bit group-quantised) weight GEMMs on the Llama-3-8B layer
+shapes, HBM-cold.
 
 Each shape gets enough weight copies (>= 1 GiB in all, 4x the 256 MiB Infinity Cache) that
 every GEMM of the graph-replayed chain streams its weights from HBM, as in a real decode
@@ -6,7 +7,9 @@ step; reports us per GEMM and achieved weight TB/s for M = 1 and 16 rows through
 ops.linear_dec (the decode epilogue: rstd row scale for qkv / gate|up, residual + ssq for
 o / down, fp32 logits for lm_head).
 
-    python tools/w8_decode_bench.py [--m 1,16] [--iters 20]
+With --w4 the weight bytes of a GEMM (and so the TB/s) include the float16 group parameters.
+
+    python tools/w8_decode_bench.py [--m 1,16] [--iters 20] [--w4]
 """
 import argparse
 import json
@@ -30,17 +33,21 @@ def main():
     ap.add_argument("--m", default="1,16")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--w4", action="store_true", help="4-bit group-quantised weights (csrc/gemm_w4.hip) instead of fp8")
     args = ap.parse_args()
     load_hip(required=True)
     dev = torch.device("cuda")
-    out = {}
+    out = {"weights": "w4" if args.w4 else "fp8"}
+    wbytes = {}
     for name in args.shapes.split(","):
         N, K, kind = SHAPES[name]
-        copies = max(2, (1 << 30) // (N * K))
-        ws = []
-        for _ in range(copies):
-            w8, s = ops.quantize_fp8_rows(torch.randn(N, K, device=dev) * K ** -0.5)
-            ws.append((w8, s))
+        quant = ops.quantize_w4_rows if args.w4 else ops.quantize_fp8_rows
+        w8, s = quant(torch.randn(N, K, device=dev) * K ** -0.5)
+        wbytes[name] = w8.numel() * w8.element_size() + (s.numel() * s.element_size() if args.w4 else 0)
+        copies = max(2, (1 << 30) // wbytes[name])
+        ws = [(w8, s)]
+        for _ in range(copies - 1):
+            ws.append(quant(torch.randn(N, K, device=dev) * K ** -0.5))
         for M in [int(m) for m in args.m.split(",")]:
             x = torch.randn(M, K, device=dev).bfloat16()
             res = torch.randn(M, N, device=dev).bfloat16() if kind == "resid" else None
@@ -77,15 +84,15 @@ def main():
             torch.cuda.synchronize()
             us = e0.elapsed_time(e1) * 1e3 / args.iters / copies
             out[f"{name}_M{M}_us"] = round(us, 2)
-            out[f"{name}_M{M}_TBs"] = round(N * K / us / 1e6, 2)
+            out[f"{name}_M{M}_TBs"] = round(wbytes[name] / us / 1e6, 2)
         del ws
         torch.cuda.empty_cache()
     for M in [int(m) for m in args.m.split(",")]:
         layer = sum(out.get(f"{n}_M{M}_us", 0.0) for n in ("qkv", "o", "gate_up", "down"))
         if layer:
             out[f"layer_M{M}_us"] = round(layer, 2)
-            out[f"layer_M{M}_TBs"] = round(sum(SHAPES[n][0] * SHAPES[n][1] for n in ("qkv", "o", "gate_up", "down"))
-                                           / layer / 1e6, 2)
+            out[f"layer_M{M}_TBs"] = round(sum(wbytes[n] for n in ("qkv", "o", "gate_up", "down")) / layer / 1e6, 2)
+    out["weight_bytes"] = wbytes
     print(json.dumps(out), flush=True)
 
 
