@@ -65,6 +65,24 @@ struct DecodeArgs {
 };
 hipError_t paged_decode(const DecodeArgs& a, int B, int D, hipStream_t stream);
 
+// Prefill attention of T new rows of ONE sequence over its paged cache (chunked prefill, prefix
+// reuse): query row i sits at position start_pos + i and attends cache tokens 0 .. start_pos + i;
+// the chunk's own k / v are already in the cache (rope_kv runs first).
+struct PrefillArgs {
+  const uint16_t* q;      // [T, q_ld] rotated packed QKV rows; head h at h * D
+  int64_t q_ld;
+  const uint16_t* k_cache;
+  const uint16_t* v_cache;
+  const int64_t* blocks;  // the sequence's block list, >= ceil((start_pos + T) / 64) entries
+  uint16_t* o;            // [T, o_ld] rows; head h at h * D
+  int64_t o_ld;
+  int start_pos, T, H, Hkv;
+  int num_blocks;         // pool size (block ids are clamped to it)
+  float scale_log2;
+  int kv_fp8;
+};
+hipError_t paged_prefill(const PrefillArgs& a, int D, hipStream_t stream);
+
 hipError_t rep_penalty(float* logits, int64_t ld, const int* ids, int maxn, const float* penalty, int B, int V,
                        hipStream_t stream);
 

@@ -14,6 +14,9 @@
 //    permuted token order chosen so that each lane's 8 P values are 8
 //    consecutive tokens, which the transposed V cache serves with one 16-byte
 //    load per MFMA (O^T = V^T P^T).
+//  * paged_prefill: attention of a chunk of new query rows over the paged cache (chunked
+//    prefill, prefix reuse): the decode kernel's operand scheme with (query row, head) pairs
+//    as the MFMA columns and a causal mask per column.
 //  * rep_penalty: repetition penalty on the logits of previously generated
 //    tokens (the reference accepts and ignores it, SURVEY V-7).
 #include "common.h"
@@ -616,6 +619,229 @@ hipError_t paged_decode(const DecodeArgs& a, int B, int D, hipStream_t stream) {
   else if (D == 32) PD_LAUNCH(32);
   else return hipErrorInvalidValue;
 #undef PD_LAUNCH
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------ paged prefill attention
+// Queries are T new rows of one sequence at positions start_pos.., keys / values are the paged
+// pools read through the sequence's block list (the chunk's own k / v were written by rope_kv
+// before this launch): chunked prefill and prefix reuse without a contiguous copy of the prefix.
+// Same operand scheme as paged_decode (S^T = K Q^T with K rows in the permuted token order,
+// O^T += V^T P^T from the transposed V pool), but the 16 MFMA columns are (query row, head in
+// group) pairs: column c of a workgroup <-> row c / G, head hk * G + c % G, so a G that does not
+// divide 16 wastes at most G - 1 columns per workgroup.  One workgroup of 4 waves per (tile of
+// 64 / G query rows, kv head); every wave carries all PP_NCT = 4 column tiles and walks blocks
+// wid, wid + 4, ... up to the tile's last position, so each block's K / V fragments are loaded
+// once per workgroup and reused by 64 columns; the 4 wave states merge through LDS, one column
+// tile at a time.  Causal: column at position p sees tokens <= p; their scores go to -inf before
+// the max, V lanes past the sequence end are zeroed (never-written slots may hold NaN).
+constexpr int PP_NW = 4;
+constexpr int PP_NCT = 4;
+
+template <int D, bool F8KV>
+__global__ void __launch_bounds__(64 * PP_NW) paged_prefill_kernel(PrefillArgs a) {
+  constexpr int NW = PP_NW, NCT = PP_NCT;
+  constexpr int KS = D / 32;   // k-steps of S^T over the head dim
+  constexpr int NB = D / 16;   // 16-wide d blocks of O^T
+  __shared__ float sm_ml[NW][2][16];
+  __shared__ float sm_o[NW][D][17];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int col = lane & 15, g = lane >> 4;
+  const int hk = blockIdx.y;
+  const int G = a.H / a.Hkv;
+  const int QT = (16 * NCT) / G;                       // query rows per workgroup
+  const int row0 = blockIdx.x * QT;
+  const int rows = min(QT, a.T - row0);
+  const int S = a.start_pos + a.T;                     // tokens of the sequence in the cache
+  const int nblk = (a.start_pos + row0 + rows - 1) / KV_BLOCK + 1;   // blocks up to the tile's last position
+
+  int64_t phys = wid < nblk ? a.blocks[wid] : 0;       // first load of the chain
+
+  // Q^T fragments (B operand) of the NCT column tiles; lim = tokens the column may see (0: unused column)
+  bf16x8_t qf[NCT][KS];
+  int lim[NCT];
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+    const int c = ct * 16 + col;
+    const int rl = c / G, hg = c - rl * G;
+    const bool ok = rl < rows;
+    lim[ct] = ok ? a.start_pos + row0 + rl + 1 : 0;
+    const uint16_t* qp = a.q + (int64_t)(row0 + (ok ? rl : 0)) * a.q_ld + (int64_t)(hk * G + hg) * D;
+#pragma unroll
+    for (int t = 0; t < KS; ++t) {
+      u32x4_t w = *(const u32x4_t*)(qp + t * 32 + g * 8);
+      if (!ok) w = (u32x4_t){0u, 0u, 0u, 0u};
+      qf[ct][t] = __builtin_bit_cast(bf16x8_t, w);
+    }
+  }
+
+  f32x4_t o[NCT][NB];
+  float mrow[NCT], lrow[NCT];
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+    mrow[ct] = -INFINITY;
+    lrow[ct] = 0.f;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) o[ct][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  }
+
+  for (int bi = wid; bi < nblk; bi += NW) {
+    if (bi != wid) phys = a.blocks[bi];
+    phys = min(max(phys, (int64_t)0), (int64_t)a.num_blocks - 1);   // a bad list entry must not leave the pool
+    const int64_t kvo = (phys * a.Hkv + hk) * KV_BLOCK * D;   // elements (= bytes for fp8)
+    const uint16_t* kb = a.k_cache + kvo;
+    const uint16_t* vb = a.v_cache + kvo;
+    const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k_cache) + kvo;
+    const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v_cache) + kvo;
+    const int tok0 = bi * KV_BLOCK;
+    const int valid = min(KV_BLOCK, S - tok0);
+
+    // every K and V fragment of the block in flight at once (tile / token order: paged_decode)
+    bf16x8_t kf[4][KS];
+    bf16x8_t vf[2][NB];
+    const int64_t vro = (int64_t)col * KV_BLOCK + 8 * g;
+#pragma unroll
+    for (int kb16 = 0; kb16 < 4; ++kb16) {
+      const int tok = 32 * (kb16 >> 1) + 8 * (col >> 2) + 4 * (kb16 & 1) + (col & 3);
+#pragma unroll
+      for (int t = 0; t < KS; ++t) {
+        if constexpr (F8KV) {
+          const uint2 w = *(const uint2*)(kb8 + (int64_t)tok * D + g * 8 + t * 32);
+          kf[kb16][t] = __builtin_bit_cast(bf16x8_t, fp8x8_to_bf16(w.x, w.y));
+        } else {
+          kf[kb16][t] = *(const bf16x8_t*)(kb + (int64_t)tok * D + g * 8 + t * 32);
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        if constexpr (F8KV) {
+          const uint2 w = *(const uint2*)(vb8 + vro + 32 * s + (int64_t)j * 16 * KV_BLOCK);
+          vf[s][j] = __builtin_bit_cast(bf16x8_t, fp8x8_to_bf16(w.x, w.y));
+        } else {
+          vf[s][j] = *(const bf16x8_t*)(vb + vro + 32 * s + (int64_t)j * 16 * KV_BLOCK);
+        }
+      }
+    // slots past the sequence end were never written: no 0 * NaN through the PV MFMA
+    if (valid < KV_BLOCK) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (32 * s + 8 * g + e >= valid) {
+#pragma unroll
+            for (int j = 0; j < NB; ++j) vf[s][j][e] = (__bf16)0.f;
+          }
+    }
+
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct) {
+      f32x4_t sc[4];
+#pragma unroll
+      for (int kb16 = 0; kb16 < 4; ++kb16) {
+        sc[kb16] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < KS; ++t)
+          sc[kb16] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kb16][t], qf[ct][t], sc[kb16], 0, 0, 0);
+      }
+      const int seen = lim[ct] - tok0;   // tokens of this block the column may see
+      float mx = mrow[ct];
+#pragma unroll
+      for (int kb16 = 0; kb16 < 4; ++kb16)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int tok = 32 * (kb16 >> 1) + 8 * g + 4 * (kb16 & 1) + r;
+          const float sv = tok < seen ? sc[kb16][r] * a.scale_log2 : -INFINITY;
+          sc[kb16][r] = sv;
+          mx = fmaxf(mx, sv);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float mbase = mx == -INFINITY ? 0.f : mx;
+      const float alpha = __builtin_amdgcn_exp2f(mrow[ct] - mbase);
+      float rs = 0.f;
+#pragma unroll
+      for (int kb16 = 0; kb16 < 4; ++kb16)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = __builtin_amdgcn_exp2f(sc[kb16][r] - mbase);
+          sc[kb16][r] = p;
+          rs += p;
+        }
+      rs += __shfl_xor(rs, 16, 64);
+      rs += __shfl_xor(rs, 32, 64);
+      lrow[ct] = lrow[ct] * alpha + rs;
+      mrow[ct] = mx;
+#pragma unroll
+      for (int j = 0; j < NB; ++j) o[ct][j] *= alpha;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        bf16x8_t pf;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          pf[r] = (__bf16)sc[2 * s][r];
+          pf[4 + r] = (__bf16)sc[2 * s + 1][r];
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) o[ct][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[s][j], pf, o[ct][j], 0, 0, 0);
+      }
+    }
+  }
+
+  // ---- merge the NW wave states through LDS, one column tile at a time
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+    if (ct > 0) __syncthreads();
+    if (g == 0) {
+      sm_ml[wid][0][col] = mrow[ct];
+      sm_ml[wid][1][col] = lrow[ct];
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sm_o[wid][j * 16 + 4 * g + r][col] = o[ct][j][r];
+    __syncthreads();
+    for (int idx = tid; idx < 16 * D; idx += 64 * NW) {
+      const int qc = idx / D, d = idx - qc * D;
+      const int c = ct * 16 + qc;
+      const int rl = c / G, hg = c - rl * G;
+      if (rl >= rows) continue;
+      float M = -INFINITY;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) M = fmaxf(M, sm_ml[w][0][qc]);
+      float L = 0.f, O = 0.f;
+      if (M != -INFINITY) {
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+          const float e = __builtin_amdgcn_exp2f(sm_ml[w][0][qc] - M);
+          L += sm_ml[w][1][qc] * e;
+          O += sm_o[w][d][qc] * e;
+        }
+      }
+      a.o[(int64_t)(row0 + rl) * a.o_ld + (int64_t)(hk * G + hg) * D + d] = f2bf(L > 0.f ? O / L : 0.f);
+    }
+  }
+}
+
+hipError_t paged_prefill(const PrefillArgs& a, int D, hipStream_t stream) {
+  if (a.T <= 0) return hipSuccess;
+  if (a.Hkv <= 0 || a.H % a.Hkv != 0 || a.H / a.Hkv > 16 || a.num_blocks <= 0 || a.start_pos < 0) return hipErrorInvalidValue;
+  const int QT = (16 * PP_NCT) / (a.H / a.Hkv);
+  dim3 grid((a.T + QT - 1) / QT, a.Hkv), block(64 * PP_NW);
+#define PP_LAUNCH(D_)                                                                            \
+  do {                                                                                           \
+    if (a.kv_fp8) hipLaunchKernelGGL((paged_prefill_kernel<D_, true>), grid, block, 0, stream, a); \
+    else hipLaunchKernelGGL((paged_prefill_kernel<D_, false>), grid, block, 0, stream, a);         \
+  } while (0)
+  if (D == 64) PP_LAUNCH(64);
+  else if (D == 128) PP_LAUNCH(128);
+  else if (D == 32) PP_LAUNCH(32);
+  else return hipErrorInvalidValue;
+#undef PP_LAUNCH
   return hipGetLastError();
 }
 

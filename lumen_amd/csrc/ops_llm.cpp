@@ -1,5 +1,5 @@
 // torch.ops.lumen.* registration of the decoder-LLM kernels (llm.hip): fused RoPE +
-// paged KV-cache write, paged flash-decoding attention, repetition penalty.
+// paged KV-cache write, paged flash-decoding attention, paged prefill attention, repetition penalty.
 #include <ATen/ATen.h>
 #include <ATen/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -138,6 +138,40 @@ void paged_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tens
   CHECK_HIP3(lumen::paged_decode(a, (int)B, (int)D, cur()));
 }
 
+// q [T, >= H D] rows of the rotated packed QKV buffer (bf16); blocks int64 [>= ceil((start_pos + T) / 64)]:
+// the sequence's block list; out [T, >= H D] rows.  One sequence per call.
+void paged_prefill(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache, const at::Tensor& blocks,
+                   int64_t start_pos, int64_t H, int64_t Hkv, double scale, at::Tensor out) {
+  TORCH_CHECK(k_cache.dim() == 4, "k_cache: [NB, Hkv, 64, D]");
+  const int64_t D = k_cache.size(3);
+  const int kv_fp8 = check_cache(k_cache, v_cache, Hkv, D);
+  TORCH_CHECK(D == 32 || D == 64 || D == 128, "paged_prefill: head dim 32, 64 or 128");
+  TORCH_CHECK(Hkv > 0 && H % Hkv == 0 && H / Hkv <= 16, "paged_prefill: at most 16 query heads per kv head");
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && q.dim() == 2 && q.stride(1) == 1 && q.size(1) >= H * D &&
+              q.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0, "paged_prefill: q rows");
+  const int64_t T = q.size(0);
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 && out.dim() == 2 && out.stride(1) == 1 &&
+              out.size(1) >= H * D && out.size(0) == T, "paged_prefill: out rows");
+  TORCH_CHECK(q.device() == k_cache.device() && out.device() == q.device() && v_cache.device() == q.device() &&
+              blocks.device() == q.device(), "paged_prefill: tensors on one device");
+  TORCH_CHECK(blocks.scalar_type() == at::kLong && blocks.dim() == 1 && blocks.is_contiguous(), "blocks int64 [n]");
+  TORCH_CHECK(start_pos >= 0 && start_pos + T < (int64_t(1) << 31), "paged_prefill: start_pos");
+  TORCH_CHECK(blocks.numel() * lumen::KV_BLOCK >= start_pos + T, "paged_prefill: block list shorter than start_pos + T");
+  if (T == 0) return;
+  lumen::PrefillArgs a{};
+  a.q = bfp(q); a.q_ld = q.stride(0);
+  a.k_cache = reinterpret_cast<const uint16_t*>(k_cache.data_ptr());
+  a.v_cache = reinterpret_cast<const uint16_t*>(v_cache.data_ptr());
+  a.blocks = blocks.data_ptr<int64_t>();
+  a.o = bfp(out); a.o_ld = out.stride(0);
+  a.start_pos = (int)start_pos; a.T = (int)T; a.H = (int)H; a.Hkv = (int)Hkv;
+  a.num_blocks = (int)k_cache.size(0);
+  a.scale_log2 = (float)(scale * 1.4426950408889634);
+  a.kv_fp8 = kv_fp8;
+  const at::DeviceGuard g(q.device());
+  CHECK_HIP3(lumen::paged_prefill(a, (int)D, cur()));
+}
+
 // profiling: per-workgroup timestamps of paged_decode into dbg [B, Hkv, nsplit, 8] int64 (empty: off)
 void decode_set_dbg(const at::Tensor& dbg) {
   TORCH_CHECK(dbg.is_cuda() && dbg.scalar_type() == at::kLong && dbg.is_contiguous(), "decode_set_dbg: int64");
@@ -178,6 +212,8 @@ TORCH_LIBRARY_FRAGMENT(lumen, m) {
         "Tensor(o!) out, int H, int Hkv, float scale, int nsplit, int blocks_per_split, Tensor(p!)? part_o=None, "
         "Tensor(m!)? part_ml=None, Tensor? pos=None, Tensor? cos_sin=None, Tensor? slots=None, Tensor? pf0=None, "
         "Tensor? pf1=None) -> ()");
+  m.def("paged_prefill(Tensor q, Tensor k_cache, Tensor v_cache, Tensor blocks, int start_pos, int H, int Hkv, "
+        "float scale, Tensor(a!) out) -> ()");
   m.def("rep_penalty_(Tensor(a!) logits, Tensor ids, Tensor penalty) -> ()");
   m.def("decode_set_dbg(Tensor dbg) -> ()");
 }
@@ -185,6 +221,7 @@ TORCH_LIBRARY_FRAGMENT(lumen, m) {
 TORCH_LIBRARY_IMPL(lumen, CUDA, m) {
   m.impl("rope_kv", &rope_kv);
   m.impl("paged_decode", &paged_decode);
+  m.impl("paged_prefill", &paged_prefill);
   m.impl("rep_penalty_", &rep_penalty_);
   m.impl("upload_small", &upload_small);
   m.impl("decode_set_dbg", &decode_set_dbg);

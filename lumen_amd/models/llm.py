@@ -48,6 +48,14 @@ _FUSED_DECODE_ROPE = True
 # to a communication stream, so half A's all-reduce overlaps half B's GEMMs (624-token
 # LLaVA prompts at TP 8: 64 x 5 MB all-reduces on the time-to-first-token path)
 _TP_OVERLAP_MIN_ROWS = 256
+# chunked prefill / prefix reuse (start_pos > 0): chunks of up to this many rows attend the paged
+# cache through the paged-prefill kernel (csrc/llm.hip).  Larger chunks, and LUMEN_PAGED_PREFILL=0,
+# gather the prefix out of the pools and run the flash kernel on the copy: at the Llama-3-8B layer
+# shape the kernel takes 0.55-0.89x the gather path's time up to 512 rows (contexts to 8k, bf16 and
+# fp8 caches) but 1.06-1.9x from 1024 rows up, where its workgroups (one per CU at a time: the K / V
+# fragments of a block fill the register file) no longer fit one round over the 256 CUs
+# (profiles/prefix_cache_kernel_v1.txt)
+_PAGED_PREFILL_MAX_ROWS = 512
 # (r4's fused MX prefill chain -- block-scaled activations from the epilogues, 6 launches per
 # layer -- lost its A/B to this per-token chain, 13.12 vs 12.79 ms TTFT, profiles/r4_mx_chain_ab_v1.txt,
 # and was removed in r5; the MX W8A8 chain stays for the ViT tower, models/clip.py:run_blocks_mx)
@@ -608,15 +616,22 @@ class LLM(nn.Module):
 
         Chunked prefill (``start_pos`` > 0): ``prefix_blocks`` (int64, the sequence's KV
         blocks covering [0, start_pos + T)) — the chunk's queries attend the cached prefix
-        plus themselves (causal, last query aligned with the last key).  K/V of the prefix
-        are gathered from the paged cache (K [blk, Hkv, 64, D]; V stored transposed)."""
+        plus themselves (causal, last query aligned with the last key).  On the GPU the paged-prefill
+        kernel reads K/V of the prefix straight from the pools (``lops.paged_prefill``); the gather
+        path (LUMEN_PAGED_PREFILL=0, CPU, other head dims, chunks of more than 512 rows) copies them out of the paged cache
+        (K [blk, Hkv, 64, D]; V stored transposed) for the flash kernel."""
         self._maybe_fold(x)
         T = x.shape[0]
         pos = torch.arange(start_pos, start_pos + T, device=x.device, dtype=torch.int32)
         D = self.cfg.head_dim
         S = start_pos + T
+        paged = start_pos > 0 and x.is_cuda and D in lops.PAGED_PREFILL_HEAD_DIMS and \
+            T <= _PAGED_PREFILL_MAX_ROWS and os.environ.get("LUMEN_PAGED_PREFILL", "1") != "0"
 
         def attn(qkv, l, kc, vc):
+            if paged and l.H // l.Hkv <= 16:
+                assert prefix_blocks is not None and kc is not None, "chunked prefill needs the KV cache"
+                return lops.paged_prefill(qkv, kc, vc, prefix_blocks, start_pos, l.H, l.Hkv)
             q5 = qkv.view(1, T, l.H + 2 * l.Hkv, D)
             if start_pos > 0:
                 assert prefix_blocks is not None and kc is not None, "chunked prefill needs the KV cache"

@@ -167,6 +167,44 @@ def paged_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     return out
 
 
+PAGED_PREFILL_HEAD_DIMS = (32, 64, 128)
+
+
+def paged_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, blocks: torch.Tensor,
+                  start_pos: int, H: int, Hkv: int, scale: Optional[float] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention of T new rows of ONE sequence over its paged cache: q [T, >= H*D] (rows of the
+    rotated packed QKV buffer, may be a view), ``blocks`` int64 the sequence's block list
+    covering positions [0, start_pos + T).  Row i sits at position start_pos + i and attends
+    cache tokens 0 .. start_pos + i; the rows' own k / v must already be in the cache
+    (:func:`rope_kv` with slots).  Returns out [T, H*D].  Head dims 32 / 64 / 128 on the GPU."""
+    T = q.shape[0]
+    D = k_cache.shape[3]
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    if out is None:
+        out = torch.empty((T, H * D), device=q.device, dtype=q.dtype)
+    if q.is_cuda:
+        hip_ops().paged_prefill(q, k_cache, v_cache, blocks, int(start_pos), int(H), int(Hkv), float(scale), out)
+        return out
+    if T == 0:
+        return out
+    G = H // Hkv
+    S = start_pos + T
+    nb = -(-S // KV_BLOCK)
+    if blocks.numel() < nb:
+        raise ValueError("paged_prefill: block list shorter than start_pos + T")
+    bl = blocks[:nb].long()
+    k = k_cache[bl].float().permute(1, 0, 2, 3).reshape(Hkv, nb * KV_BLOCK, D)[:, :S]
+    v = v_cache[bl].float().permute(1, 0, 3, 2).reshape(Hkv, nb * KV_BLOCK, D)[:, :S]
+    qb = q[:, :H * D].float().view(T, Hkv, G, D)
+    s = torch.einsum("thgd,hsd->hgts", qb, k) * scale
+    hidden = torch.arange(S)[None, :] > (start_pos + torch.arange(T))[:, None]       # [T, S]
+    p = torch.softmax(s.masked_fill(hidden, float("-inf")), -1)
+    o = torch.einsum("hgts,hsd->thgd", p, v)
+    out[:, :H * D] = o.reshape(T, H * D).to(out.dtype)
+    return out
+
+
 def rep_penalty_(logits: torch.Tensor, token_ids: Sequence[Sequence[int]], penalty: Sequence[float]) -> torch.Tensor:
     """logits[b, t] /= p (if > 0) or *= p for every distinct previously seen token t."""
     B = logits.shape[0]

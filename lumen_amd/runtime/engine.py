@@ -16,7 +16,12 @@ host<->device every token (packages/lumen-vlm/src/lumen_vlm/backends/onnxrt_back
   cached prefix: :meth:`LLM.prefill` ``prefix_blocks``);
 * all running requests then advance together: one batched decode step per
   iteration (paged flash-decoding), sampling from on-device top-k candidates;
-* finished sequences release their blocks.
+* finished sequences release their blocks;
+* prefix reuse (``submit(prefix_keys=...)`` / :meth:`LLMEngine.match_prefix`): a prompt whose
+  leading 64-token blocks carry the content keys of an earlier prompt starts from that prompt's
+  KV blocks and prefills only the rest (the chunk path above, ``start_pos`` = the hit); a prompt
+  publishes its full blocks to the block manager's index once its prefill succeeded.  Not under
+  tensor parallelism: with ``tp_sync`` the keys are ignored.
 
 Tensor parallelism: rank 0 runs this loop and broadcasts every step (prefill inputs,
 decode token ids / positions / slots / block tables) to follower ranks running
@@ -76,6 +81,8 @@ class GenRequest:
     rng: Any = None
     x: Any = None                           # prefill input embeddings while the prompt is being chunk-prefilled
     done: int = 0                           # prompt tokens prefilled so far
+    cached_tokens: int = 0                  # leading prompt tokens taken from the prefix index (not computed)
+    prefix_keys: Any = None                 # uint64 [n, 2] content keys of the prompt's full blocks
 
     def stream(self, timeout: Optional[float] = None) -> Iterator[tuple]:
         """yields ("token", id) ... then ("done", reason) | raises the engine error."""
@@ -86,6 +93,14 @@ class GenRequest:
             yield kind, val
             if kind == "done":
                 return
+
+
+@dataclass
+class PrefixHit:
+    """A prefix match held for a request that is still being built: sequence ``rid`` exists in
+    the block manager and shares the blocks of the first ``tokens`` prompt tokens."""
+    rid: int
+    tokens: int
 
 
 class Sampler:
@@ -588,7 +603,8 @@ class LLMEngine:
         self._ws: dict = {}
         self._pending: Optional[tuple] = None     # (request ids, handle) of a look-ahead decode step in flight
         self.device = llm.embed.device
-        self.stats = {"prefills": 0, "prefill_chunks": 0, "decode_steps": 0, "tokens": 0}
+        self.stats = {"prefills": 0, "prefill_chunks": 0, "decode_steps": 0, "tokens": 0,
+                      "prefix_hits": 0, "prefix_tokens": 0, "prefill_tokens": 0}
         if use_graphs is None:
             use_graphs = os.environ.get("LUMEN_HIP_GRAPHS", "1") == "1"
         self.graphs: Optional[DecodeGraphs] = None
@@ -603,16 +619,62 @@ class LLMEngine:
         self._thread.start()
 
     # ------------------------------------------------------------------ public API
-    def submit(self, prefill_args: Any, prompt_len: int, params: SamplingParams) -> GenRequest:
-        if self._stop.is_set():
-            raise RuntimeError("engine stopped")
-        need = prompt_len + params.max_new_tokens
-        if need > self.kv.capacity_tokens:
-            raise ValueError(f"request needs {need} KV tokens, cache holds {self.kv.capacity_tokens}")
+    @staticmethod
+    def _hit_cap(prompt_len: int) -> int:
+        """blocks a hit may cover: the prompt's last row is always computed (it yields the logits)"""
+        return max(0, (prompt_len - 1) // BLOCK)
+
+    def match_prefix(self, prefix_keys, prompt_len: Optional[int] = None) -> PrefixHit:
+        """Match ``prefix_keys`` (uint64 [n, 2], one chained content key per full 64-token block
+        of a prompt) against the prefix index under a fresh request id and hold the matched
+        blocks.  Pass the hit to :meth:`submit` (``hit=``) or give it back with
+        :meth:`release_prefix`.  ``prompt_len`` caps the hit so that the last row is computed.
+        Tensor parallelism: no reuse, the hit is empty."""
+        rid = next(self._ids)
+        if prefix_keys is None or self.sync is not None:
+            return PrefixHit(rid, 0)
+        keys = np.ascontiguousarray(prefix_keys, dtype=np.uint64).reshape(-1, 2)
+        if prompt_len is not None:
+            keys = keys[:self._hit_cap(prompt_len)]
+        return PrefixHit(rid, self.kv.blocks.match(keys, rid))
+
+    def release_prefix(self, hit: Optional[PrefixHit]) -> None:
+        """Drop the references of a hit whose request is abandoned before submit."""
+        if hit is not None and hit.tokens > 0:
+            self.kv.blocks.release(hit.rid)
+            hit.tokens = 0
+
+    def submit(self, prefill_args: Any, prompt_len: int, params: SamplingParams, prefix_keys=None,
+               hit: Optional[PrefixHit] = None) -> GenRequest:
+        """``prefix_keys``: uint64 [n, 2], key i covering prompt tokens [64 i, 64 i + 64) and chaining
+        key i - 1 -- the prompt may start from cached blocks and publishes its own after prefill.
+        ``hit``: the result of an earlier :meth:`match_prefix` with the same keys (the request
+        takes over its id and references).  The prefill builder must return all ``prompt_len``
+        rows; rows before the hit are never read."""
+        try:
+            if self._stop.is_set():
+                raise RuntimeError("engine stopped")
+            need = prompt_len + params.max_new_tokens
+            if need > self.kv.capacity_tokens:
+                raise ValueError(f"request needs {need} KV tokens, cache holds {self.kv.capacity_tokens}")
+        except Exception:
+            self.release_prefix(hit)
+            raise
         if prompt_len + params.max_new_tokens > self.llm.cfg.max_position:
             params.max_new_tokens = max(1, self.llm.cfg.max_position - prompt_len)
-        r = GenRequest(rid=next(self._ids), prefill_args=prefill_args, prompt_len=prompt_len, params=params,
-                       t_submit=time.perf_counter(), rng=np.random.default_rng(params.seed))
+        keys = None
+        if prefix_keys is not None and self.sync is None:
+            keys = np.ascontiguousarray(prefix_keys, dtype=np.uint64).reshape(-1, 2)[:prompt_len // BLOCK]
+        if hit is None:
+            hit = self.match_prefix(keys, prompt_len)
+        elif hit.tokens > self._hit_cap(prompt_len) * BLOCK:
+            # matched without the prompt length: give the last block back
+            self.release_prefix(hit)
+            if keys is not None:
+                hit.tokens = self.kv.blocks.match(keys[:self._hit_cap(prompt_len)], hit.rid)
+        r = GenRequest(rid=hit.rid, prefill_args=prefill_args, prompt_len=prompt_len, params=params,
+                       t_submit=time.perf_counter(), rng=np.random.default_rng(params.seed),
+                       cached_tokens=hit.tokens, prefix_keys=keys)
         self._waiting.put(r)
         return r
 
@@ -688,8 +750,14 @@ class LLMEngine:
                     raise RuntimeError(f"prefill built {x.shape[0]} rows for a {r.prompt_len}-token prompt")
             else:
                 x = self.build(r.prefill_args)
+                if r.cached_tokens and x.shape[0] != r.prompt_len:
+                    raise RuntimeError(f"prefill built {x.shape[0]} rows for a {r.prompt_len}-token prompt "
+                                       f"with {r.cached_tokens} cached tokens")
                 r.prompt_len = x.shape[0]
-            r.x, r.done = x, 0
+            r.x, r.done = x, r.cached_tokens
+            if r.cached_tokens:
+                self.stats["prefix_hits"] += 1
+                self.stats["prefix_tokens"] += r.cached_tokens
         T = r.prompt_len
         s = r.done
         e = min(T, s + max(1, budget))
@@ -703,12 +771,17 @@ class LLMEngine:
                                   prefix_blocks=h2d_ahead(tab, self.device) if tab is not None else None)
         r.done = e
         self.stats["prefill_chunks"] += 1
+        self.stats["prefill_tokens"] += e - s
         if not last:
             return e - s
         r.x = None
         r.ctx = T
         tok = self.sampler.pick(self.sampler.candidates(logits, spec), [r])[0]
         r.t_first = time.perf_counter()
+        # the whole prompt is in the cache (the token read above waited for it): its full blocks
+        # become matchable.  Later requests run on this stream too, so they read after these writes.
+        if r.prefix_keys is not None and len(r.prefix_keys):
+            self.kv.blocks.publish(r.rid, r.prefix_keys[:T // BLOCK])
         self.stats["prefills"] += 1
         self._prefilling.remove(r)
         if self._emit(r, tok):

@@ -30,7 +30,7 @@ class BlockManager:
         self.lib = lib
         lib.lumen_kv_create.restype = ctypes.c_void_p
         lib.lumen_kv_create.argtypes = [ctypes.c_int]
-        for fn in ("lumen_kv_free_blocks", "lumen_kv_num_seqs"):
+        for fn in ("lumen_kv_free_blocks", "lumen_kv_num_seqs", "lumen_kv_cached_blocks"):
             getattr(lib, fn).argtypes = [ctypes.c_void_p]
         lib.lumen_kv_destroy.argtypes = [ctypes.c_void_p]
         lib.lumen_kv_reserve.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]
@@ -38,6 +38,9 @@ class BlockManager:
         lib.lumen_kv_table.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         lib.lumen_kv_fork.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
         lib.lumen_kv_release.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        lib.lumen_kv_publish.argtypes = [ctypes.c_void_p, ctypes.c_int64, u64p, ctypes.c_int]
+        lib.lumen_kv_match.argtypes = [ctypes.c_void_p, u64p, ctypes.c_int, ctypes.c_int64]
         self.num_blocks = num_blocks
         self.h = lib.lumen_kv_create(num_blocks)
 
@@ -73,6 +76,38 @@ class BlockManager:
 
     def release(self, seq: int) -> None:
         self.lib.lumen_kv_release(self.h, seq)
+
+    # ---- prefix index: full blocks of finished prompts, found again by content key
+    @staticmethod
+    def _keys(keys) -> np.ndarray:
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        if k.ndim != 2 or k.shape[1] != 2:
+            raise ValueError("prefix keys: uint64 [n, 2]")
+        return k
+
+    def publish(self, seq: int, keys) -> int:
+        """Register the first ``len(keys)`` blocks of ``seq`` (all full) under ``keys`` [n, 2] uint64;
+        returns how many were new to the index."""
+        k = self._keys(keys)
+        n = self.lib.lumen_kv_publish(self.h, seq, k.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(k))
+        if n < 0:
+            raise KeyError(f"publish: sequence {seq} unknown or shorter than {len(k)} full blocks")
+        return n
+
+    def match(self, keys, dst: int) -> int:
+        """Create ``dst`` sharing the blocks of the longest leading run of ``keys`` in the index;
+        returns the tokens covered (0: no match, ``dst`` not created)."""
+        k = self._keys(keys)
+        if len(k) == 0:
+            return 0
+        n = self.lib.lumen_kv_match(self.h, k.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(k), dst)
+        if n < 0:
+            raise KeyError(f"match: sequence {dst} exists")
+        return n
+
+    def cached_blocks(self) -> int:
+        """blocks held by the prefix index alone (counted as free: a reserve may evict them)"""
+        return self.lib.lumen_kv_cached_blocks(self.h)
 
 
 def kv_dtype_from_env(default=torch.bfloat16):

@@ -76,6 +76,14 @@ def kv_blocks_used():
     return _get("Gauge", "lumen_kv_blocks_used", "paged KV blocks in use", ())
 
 
+def prefix_cached_tokens_total():
+    return _get("Counter", "lumen_vlm_prefix_cached_tokens_total", "prompt tokens served from the prefix KV cache", ())
+
+
+def kv_blocks_cached():
+    return _get("Gauge", "lumen_kv_blocks_cached", "paged KV blocks held only by the prefix index", ())
+
+
 def observe_request(service: str, task: str, status: str, seconds: float) -> None:
     c, h = requests_total(), request_seconds()
     if c is not None:

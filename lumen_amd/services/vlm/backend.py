@@ -21,6 +21,7 @@ batching over a paged KV cache) — concurrent requests share decode steps.
 """
 from __future__ import annotations
 
+import hashlib
 import json
 import logging
 import os
@@ -37,7 +38,9 @@ from ...models.vlm import ENCODE_AHEAD, VLM, VLM_PRESETS, EncodedImage, Prepared
 from ...resources.exceptions import ResourceNotFoundError
 from ...runtime.engine import LLMEngine, SamplingParams
 from ...runtime.kv_cache import PagedKVCache
+from ...runtime import metrics
 from ...runtime.metrics import current_timer, stage
+from ...utils.h2d import h2d_ahead
 from ...utils.image import decode_rgb
 from ...utils.jpeg import decode_image
 from ..common import GenericResources, load_safetensors, pick_device, runtime_name
@@ -238,6 +241,35 @@ class IncrementalText:
         return delta
 
 
+class CachedImagePrefill:
+    """Prefill arguments of a request whose image rows all lie inside a prefix-cache hit: the
+    expanded token ids alone (the image is neither decoded nor encoded; the rows it would fill
+    are never read)."""
+
+    def __init__(self, full_ids: Sequence[int]):
+        self.full_ids = list(full_ids)
+
+
+def prefix_cache_keys(full_ids: Sequence[int], image_starts: Sequence[int], image_digest: bytes) -> np.ndarray:
+    """Chained content keys of a prompt's full 64-token blocks -> uint64 [n, 2]:
+    key_i = blake2b-128(key_{i-1} | ids[64 i : 64 i + 64] | image_digest), the digest (of the raw
+    request image bytes) mixed in from the first block that holds an image row onward -- the
+    placeholder ids of two different images are the same, their cache rows are not."""
+    ids = np.asarray(full_ids, dtype="<i8")
+    n = len(ids) // 64
+    keys = np.zeros((n, 2), np.uint64)
+    first_img = min(image_starts) // 64 if len(image_starts) else n
+    prev = b""
+    for i in range(n):
+        h = hashlib.blake2b(prev, digest_size=16)
+        h.update(ids[64 * i:64 * i + 64].tobytes())
+        if i >= first_img:
+            h.update(image_digest)
+        prev = h.digest()
+        keys[i] = np.frombuffer(prev, dtype="<u8")
+    return keys
+
+
 def _engine_stages(r) -> None:
     """Engine-side stage times of a finished request onto the request's timer: admission
     queue, prefill (incl. vision tower) to first token, and the decode phase."""
@@ -278,6 +310,9 @@ class MI355XVLMBackend:
         self.model: Optional[VLM] = None
         self.engine: Optional[LLMEngine] = None
         self._remote = None            # serving front end: generation runs on a GPU engine (engine_worker)
+        # prefix KV cache across requests (off by default): LUMEN_PREFIX_CACHE=1 or extra.prefix_cache
+        self.prefix_cache = os.environ.get("LUMEN_PREFIX_CACHE", "0") == "1" or \
+            str(meta.get("prefix_cache", "")).lower() in ("1", "true")
         self.load_time = 0.0
 
     # ------------------------------------------------------------------ lifecycle
@@ -529,6 +564,8 @@ class MI355XVLMBackend:
         ids, img = args[0], args[1]
         if isinstance(img, PreparedPrefill):
             return img.x
+        if isinstance(img, CachedImagePrefill):
+            return self.model.llm.embed_tokens(h2d_ahead(img.full_ids, self.device, torch.long))
         if len(args) > 2:                    # TP follower: no image here, rank 0 broadcasts its features
             return self.model.build_prefill(ids, [], n_images=args[2])
         tens = [img if isinstance(img, (torch.Tensor, EncodedImage)) else torch.from_numpy(img)] \
@@ -558,21 +595,46 @@ class MI355XVLMBackend:
         with stage("tokenize"):
             prompt = self.build_prompt(self._with_image_token(req.messages), req.add_generation_prompt)
             ids = self.tokenize(prompt)
-        try:
-            with stage("decode"):
-                # baseline JPEGs: parallel host entropy decode + GPU reconstruction (utils/jpeg.py);
-                # others: Pillow, DCT-scaled towards the vision input
-                img = decode_image(req.image_bytes, self.device, draft_to=self.jpeg_draft_size())
-        except ValueError as e:
-            raise InvalidInputError(str(e)) from e
         full, starts = self.model.expand_image_tokens(ids, 1)
-        if starts and ENCODE_AHEAD and self._tp_group is None and torch.device(self.device).type == "cuda":
-            # the prompt's embeddings and the image encoder are queued now, in this request's
-            # thread, while the engine admits it
-            with stage("encode"):
-                pre = self.model.prepare_prefill(ids, [img])
-            if pre is not None:
-                img = pre
+        keys = hit = None
+        if self.prefix_cache and not self.tp.enabled:
+            # match before touching the image: a hit that covers every image row needs neither the
+            # JPEG decode nor the vision tower
+            with stage("prefix"):
+                digest = hashlib.blake2b(req.image_bytes, digest_size=16).digest()
+                keys = prefix_cache_keys(full, starts, digest)
+                hit = self.engine.match_prefix(keys, len(full))
+        try:
+            r = self._submit_matched(req, ids, full, starts, keys, hit)
+        except BaseException:
+            self.engine.release_prefix(hit)     # no-op once the request owns the references
+            raise
+        if hit is not None:
+            c, g = metrics.prefix_cached_tokens_total(), metrics.kv_blocks_cached()
+            if c is not None:
+                c.inc(r.cached_tokens)
+                g.set(self.kv.blocks.cached_blocks())
+        return r, len(full)
+
+    def _submit_matched(self, req: GenerationRequest, ids, full, starts, keys, hit):
+        N = self.model.cfg.num_image_tokens
+        if hit is not None and hit.tokens > 0 and starts and all(s + N <= hit.tokens for s in starts):
+            img = CachedImagePrefill(full)
+        else:
+            try:
+                with stage("decode"):
+                    # baseline JPEGs: parallel host entropy decode + GPU reconstruction (utils/jpeg.py);
+                    # others: Pillow, DCT-scaled towards the vision input
+                    img = decode_image(req.image_bytes, self.device, draft_to=self.jpeg_draft_size())
+            except ValueError as e:
+                raise InvalidInputError(str(e)) from e
+            if starts and ENCODE_AHEAD and self._tp_group is None and torch.device(self.device).type == "cuda":
+                # the prompt's embeddings and the image encoder are queued now, in this request's
+                # thread, while the engine admits it
+                with stage("encode"):
+                    pre = self.model.prepare_prefill(ids, [img])
+                if pre is not None:
+                    img = pre
         gc = self.generation_config
         stops = {gc.eos_token_id}
         extra_eos = self.resources.extra.get("stop_token_ids") or []
@@ -580,8 +642,10 @@ class MI355XVLMBackend:
         sp = SamplingParams(max_new_tokens=max(1, int(req.max_new_tokens)), temperature=float(req.temperature),
                             top_p=float(req.top_p), repetition_penalty=float(req.repetition_penalty),
                             stop_token_ids=tuple(stops), seed=req.extra.get("seed"))
-        r = self.engine.submit((ids, img if starts else None), len(full), sp)
-        return r, len(full)
+        r = self.engine.submit((ids, img if starts else None), len(full), sp, prefix_keys=keys, hit=hit)
+        if hit is not None:
+            hit.tokens = 0      # the request owns the references now
+        return r
 
     def _remote_result(self, request: GenerationRequest) -> GenerationResult:
         """One generation on the engine, completed on its own (not with a merged batch)."""
@@ -617,6 +681,7 @@ class MI355XVLMBackend:
         reason = "stop_sequence" if stop else (r.finish_reason or "stop")
         return GenerationResult(text=cut, tokens=list(r.tokens), finish_reason=reason,
                                 metadata={"tokens_generated": len(r.tokens), "input_tokens": n_in,
+                                          "cached_tokens": r.cached_tokens,
                                           "ttft_ms": (r.t_first - r.t_submit) * 1000 if r.t_first else None})
 
     def _generate_stream(self, request: GenerationRequest) -> Iterator[GenerationChunk]:
@@ -647,7 +712,8 @@ class MI355XVLMBackend:
                             finished = True
                             _engine_stages(r)
                             yield GenerationChunk(text="", is_final=True, metadata={"reason": "stop_sequence",
-                                                                                   "input_tokens": n_in})
+                                                                                   "input_tokens": n_in,
+                                                                                   "cached_tokens": r.cached_tokens})
                             return
                     if len(inc.text) == emitted:
                         continue                # held back: an incomplete UTF-8 tail
@@ -660,7 +726,8 @@ class MI355XVLMBackend:
                     if len(inc.text) > emitted or pending:
                         yield GenerationChunk(text=inc.text[emitted:], tokens=pending, metadata={"step": step, "t_wall": time.time()})
                     _engine_stages(r)
-                    yield GenerationChunk(text="", is_final=True, metadata={"reason": val, "input_tokens": n_in})
+                    yield GenerationChunk(text="", is_final=True, metadata={"reason": val, "input_tokens": n_in,
+                                                                           "cached_tokens": r.cached_tokens})
         finally:
             if not finished:            # the consumer went away (client cancel): stop generating
                 self.engine.cancel(r)

@@ -236,7 +236,8 @@ class GeneralFastVLMService(BaseInferenceService):
         body = self._result_bytes(res.text, res.finish_reason, len(res.tokens), n_in,
                                   {"temperature": p["temperature"], "top_p": p["top_p"],
                                    "max_tokens": p["max_new_tokens"]})
-        m = {"generated_tokens": str(len(res.tokens)), "finish_reason": res.finish_reason}
+        m = {"generated_tokens": str(len(res.tokens)), "finish_reason": res.finish_reason,
+             "cached_tokens": str(int(res.metadata.get("cached_tokens") or 0))}
         if res.metadata.get("ttft_ms") is not None:
             m["ttft_ms"] = f"{res.metadata['ttft_ms']:.2f}"
         return body, rs.MIME_TEXT_GEN, m
@@ -257,7 +258,8 @@ class GeneralFastVLMService(BaseInferenceService):
                                                "max_tokens": p["max_new_tokens"], "streaming_chunks": n_chunks,
                                                "generation_time_ms": (time.perf_counter() - t0) * 1000})
                     yield body, rs.MIME_TEXT_GEN, {"generated_tokens": str(n_tok), "finish_reason": reason,
-                                                   "streaming_chunks": str(n_chunks)}, True
+                                                   "streaming_chunks": str(n_chunks),
+                                                   "cached_tokens": str(int(ch.metadata.get("cached_tokens") or 0))}, True
                     return
                 n_tok += len(ch.tokens)
                 if ch.text:
