@@ -45,8 +45,9 @@ struct DecodeArgs {
   int H, Hkv, nsplit, blocks_per_split;
   float scale_log2;
   // fused RoPE + cache write (decode, D = 64 / 128): q comes unrotated from the QKV projection
-  // and is rotated in registers; the split owning the sequence's last block rotates the current
-  // token's k and writes k / v to slots[b] before its attention loop reads that block
+  // and is rotated in registers; the split owning the sequence's last block takes the current
+  // token's k (rotated) and v from registers for its own attention and writes them to slots[b]
+  // after its attention loop (fire-and-forget: the next decode step is the first to read them)
   const int* pos;         // [B] positions (null = q / cache already prepared by rope_kv)
   const float* cos_sin;   // [max_pos, D/2, 2]
   const int64_t* slots;   // [B]

@@ -10,17 +10,19 @@
 //    online softmax, the 4 wave states are merged through LDS and — when the
 //    context is split across workgroups — the last split to finish merges them
 //    (in-launch, ticket counter; no combine kernel).
-//    Both MFMA operands come straight from HBM: S^T = K Q^T reads K rows in a
-//    permuted token order chosen so that each lane's 8 P values are 8
-//    consecutive tokens, which the transposed V cache serves with one 16-byte
-//    load per MFMA (O^T = V^T P^T).
 //  * paged_prefill: attention of a chunk of new query rows over the paged cache (chunked
-//    prefill, prefix reuse): the decode kernel's operand scheme with (query row, head) pairs
-//    as the MFMA columns and a causal mask per column.
+//    prefill, prefix reuse) with (query row, head) pairs as the MFMA columns and a causal
+//    mask per column.
+//    Both paged kernels are bookkeeping around ONE block step, paged_attn.h: the K / V
+//    fragment loads straight from HBM (S^T = K Q^T reads K rows in a permuted token order
+//    chosen so that each lane's 8 P values are 8 consecutive tokens, which the transposed
+//    V cache serves with one 16-byte load per MFMA of O^T = V^T P^T), the online-softmax /
+//    PV step, and the LDS merge of the wave states.
 //  * rep_penalty: repetition penalty on the logits of previously generated
 //    tokens (the reference accepts and ignores it, SURVEY V-7).
 #include "common.h"
 #include "llm.h"
+#include "paged_attn.h"
 
 namespace lumen {
 
@@ -176,12 +178,15 @@ hipError_t rope_kv(const RopeKVArgs& a, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------------------ paged decode attention
-// One workgroup of NW = 4 waves per (split, kv head, sequence); wave w takes the split's 64-token
-// blocks w, w + 4, ... (up to 32 splits of 4 blocks -- 8k tokens -- one block per wave, so a
-// context of <= 256 tokens is ONE workgroup per kv head; longer contexts loop with an online
-// softmax).  The latency chain per wave is: block-table entry -> every K and V fragment of the
-// block in flight at once -> S^T = K Q^T, online softmax, O^T += V^T P^T; the 8 wave states
-// merge through LDS.  Fused RoPE mode (decode): q and the current token's k are rotated in
+// One workgroup of PA_NW = 4 waves per (split, kv head, sequence); wave w takes the split's
+// 64-token blocks w, w + 4, ...  The launch has at most 32 splits (ops/llm.py decode_splits):
+// batched decode gives a split >= 4 blocks, so a context of <= 256 tokens is ONE workgroup per kv
+// head; a few sequences get no minimum, so their blocks spread over all launched splits.  Either
+// way a wave has one block up to 8k tokens (32 splits x 4 waves); past that the waves loop over
+// their blocks with an online softmax.  The latency chain per wave is:
+// block-table entry -> every K and V fragment of the block in flight at once -> S^T = K Q^T,
+// online softmax, O^T += V^T P^T (the block step of paged_attn.h); the 4 wave states merge
+// through LDS.  Fused RoPE mode (decode): q and the current token's k are rotated in
 // registers, and the current token enters the wave that owns its block straight from registers
 // (its score q . k_cur as a lane-group dot product, its v into the V fragment) -- the cache
 // write of that token is fire-and-forget (the next step reads it), so no workgroup waits for a
@@ -190,13 +195,11 @@ hipError_t rope_kv(const RopeKVArgs& a, hipStream_t stream) {
 // stores, draws a ticket from the (sequence, kv head) counter, and the last to arrive merges
 // all splits (sc1 loads, 8 in flight) -- no combine launch, no fences (MI355X_MICROARCH.md
 // hand-off rules); the last arriver re-zeroes the counter for the next launch.
-// 4 waves = 1 per SIMD: the 512-VGPR budget holds a whole block's K and V fragments.  The launch
-// fixes the number of splits (grid.x); blocks per split = max(a.blocks_per_split, ceil(blocks /
-// grid.x)) is derived from each sequence's own ctx_len on the device, so a graph captured for the
-// longest context spreads every shorter one over all its splits as well.  (One-wave workgroups with
-// one block each measured 2x slower: their single-wave split combine is latency-serial,
-// profiles/r3_decode_attn_splits_v1.txt.)
-constexpr int PD_NW = 4;
+// The launch fixes the number of splits (grid.x); blocks per split = max(a.blocks_per_split,
+// ceil(blocks / grid.x)) is derived from each sequence's own ctx_len on the device, so a graph
+// captured for the longest context spreads every shorter one over all its splits as well.
+// (One-wave workgroups with one block each measured 2x slower: their single-wave split combine is
+// latency-serial, profiles/r3_decode_attn_splits_v1.txt.)
 
 // Prefetch workgroups (blockIdx.z >= B): stream a.pf[] once through the memory-side cache.
 __device__ __forceinline__ void pd_prefetch(const DecodeArgs& a, int wg, int nwg) {
@@ -253,8 +256,8 @@ __device__ __forceinline__ __bf16 as_cached(__bf16 v) {
 }
 
 template <int D, bool F8KV>
-__global__ void __launch_bounds__(64 * PD_NW) paged_decode_kernel(DecodeArgs a, int B) {
-  constexpr int NW = PD_NW;
+__global__ void __launch_bounds__(64 * PA_NW) paged_decode_kernel(DecodeArgs a, int B) {
+  constexpr int NW = PA_NW;
   if ((int)blockIdx.z >= B) {   // MALL prefetch workgroups
     pd_prefetch(a, ((blockIdx.z - B) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x,
                 (gridDim.z - B) * gridDim.y * gridDim.x);
@@ -263,8 +266,7 @@ __global__ void __launch_bounds__(64 * PD_NW) paged_decode_kernel(DecodeArgs a, 
   const int64_t t_start = a.dbg ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
   constexpr int KS = D / 32;   // k-steps of S^T over the head dim
   constexpr int NB = D / 16;   // 16-wide d blocks of O^T
-  __shared__ float sm_ml[NW][2][16];
-  __shared__ float sm_o[NW][D][17];
+  __shared__ WaveMerge<D> sm;
   __shared__ int sm_last;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -332,44 +334,11 @@ __global__ void __launch_bounds__(64 * PD_NW) paged_decode_kernel(DecodeArgs a, 
 
   for (int bi = blk0 + wid; bi < blk1; bi += NW) {
     if (bi != blk0 + wid) phys = a.block_table[(int64_t)b * a.bt_stride + bi];
-    const int64_t kvo = ((int64_t)phys * a.Hkv + hk) * KV_BLOCK * D;   // elements (= bytes for fp8)
-    const uint16_t* kb = a.k_cache + kvo;
-    const uint16_t* vb = a.v_cache + kvo;
-    const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k_cache) + kvo;
-    const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v_cache) + kvo;
     const int valid = min(KV_BLOCK, ctx - bi * KV_BLOCK);
-
-    // ---- every K and V fragment of the block in flight at once
-    // S^T tiles: tile kb16 = (s = kb16 >> 1, hf = kb16 & 1); MFMA row i <-> token
-    // 32s + 8(i >> 2) + 4hf + (i & 3), so C row 4g + r holds token 32s + 8g + 4hf + r.
     bf16x8_t kf[4][KS];
     bf16x8_t vf[2][NB];
-    const int64_t vro = (int64_t)col * KV_BLOCK + 8 * g;
-#pragma unroll
-    for (int kb16 = 0; kb16 < 4; ++kb16) {
-      const int tok = 32 * (kb16 >> 1) + 8 * (col >> 2) + 4 * (kb16 & 1) + (col & 3);
-#pragma unroll
-      for (int t = 0; t < KS; ++t) {
-        if constexpr (F8KV) {
-          const uint2 w = *(const uint2*)(kb8 + (int64_t)tok * D + g * 8 + t * 32);
-          kf[kb16][t] = __builtin_bit_cast(bf16x8_t, fp8x8_to_bf16(w.x, w.y));
-        } else {
-          kf[kb16][t] = *(const bf16x8_t*)(kb + (int64_t)tok * D + g * 8 + t * 32);
-        }
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        if constexpr (F8KV) {
-          const uint2 w = *(const uint2*)(vb8 + vro + 32 * s + (int64_t)j * 16 * KV_BLOCK);
-          vf[s][j] = __builtin_bit_cast(bf16x8_t, fp8x8_to_bf16(w.x, w.y));
-        } else {
-          vf[s][j] = *(const bf16x8_t*)(vb + vro + 32 * s + (int64_t)j * 16 * KV_BLOCK);
-        }
-      }
-    // the current token's v from registers (the cache store above may not have landed)
+    load_kv_block<D, F8KV>(a.k_cache, a.v_cache, ((int64_t)phys * a.Hkv + hk) * KV_BLOCK * D, col, g, kf, vf);
+    // the current token's v from registers (its cache write comes after the loop)
     const bool cur_here = owns_cur && bi == cur / KV_BLOCK;
     const int coff = cur - bi * KV_BLOCK;
     if (cur_here) {
@@ -387,12 +356,7 @@ __global__ void __launch_bounds__(64 * PD_NW) paged_decode_kernel(DecodeArgs a, 
 
     if (!q_ready) prep_q();
     f32x4_t sc[4];
-#pragma unroll
-    for (int kb16 = 0; kb16 < 4; ++kb16) {
-      sc[kb16] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < KS; ++t) sc[kb16] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kb16][t], qf[t], sc[kb16], 0, 0, 0);
-    }
+    qk_scores(kf, qf, sc);
     if (cur_here) {   // the current token's score q . k_cur from registers (rotated, rounded as cached)
       u32x4_t kw[KS];
 #pragma unroll
@@ -411,62 +375,11 @@ __global__ void __launch_bounds__(64 * PD_NW) paged_decode_kernel(DecodeArgs a, 
       for (int kb16 = 0; kb16 < 4; ++kb16)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (32 * (kb16 >> 1) + 8 * g + 4 * (kb16 & 1) + r == coff) sc[kb16][r] = dot;
+          if (pa_token(kb16, g, r) == coff) sc[kb16][r] = dot;
     }
-    float mx = mrow;
-#pragma unroll
-    for (int kb16 = 0; kb16 < 4; ++kb16)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int tok = 32 * (kb16 >> 1) + 8 * g + 4 * (kb16 & 1) + r;
-        const float sv = tok < valid ? sc[kb16][r] * a.scale_log2 : -INFINITY;
-        sc[kb16][r] = sv;
-        mx = fmaxf(mx, sv);
-      }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mbase = mx == -INFINITY ? 0.f : mx;
-    const float alpha = __builtin_amdgcn_exp2f(mrow - mbase);   // online softmax over a wave's blocks
-    float rs = 0.f;
-#pragma unroll
-    for (int kb16 = 0; kb16 < 4; ++kb16)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __builtin_amdgcn_exp2f(sc[kb16][r] - mbase);
-        sc[kb16][r] = p;
-        rs += p;
-      }
-    rs += __shfl_xor(rs, 16, 64);
-    rs += __shfl_xor(rs, 32, 64);
-    lrow = lrow * alpha + rs;
-    mrow = mx;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) o[j] *= alpha;
-
-    // a partial block: V columns past the context may hold any finite stale value (p = 0 there),
-    // but zero them anyway so that a never-written slot cannot inject a NaN through 0 * NaN
-    if (valid < KV_BLOCK) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (32 * s + 8 * g + e >= valid) {
-#pragma unroll
-            for (int j = 0; j < NB; ++j) vf[s][j][e] = (__bf16)0.f;
-          }
-    }
-    // O^T += V^T P^T over two 32-token steps; lane's P k-slots 8g + j = tokens 32s + 8g + j
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      bf16x8_t pf;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        pf[r] = (__bf16)sc[2 * s][r];
-        pf[4 + r] = (__bf16)sc[2 * s + 1][r];
-      }
-#pragma unroll
-      for (int j = 0; j < NB; ++j) o[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[s][j], pf, o[j], 0, 0, 0);
-    }
+    softmax_step(sc, valid, a.scale_log2, g, mrow, lrow, o);
+    zero_v_tail(vf, valid, g);   // after the softmax (K only): the V loads, issued last, stay in flight under it
+    pv_step(sc, vf, o);
   }
 
   if (owns_cur) {   // the current token's k (rotated) / v into the cache for the next step
@@ -507,29 +420,12 @@ __global__ void __launch_bounds__(64 * PD_NW) paged_decode_kernel(DecodeArgs a, 
     if (wid == 0) dbg[0] = t_start;
   }
   // ---- merge the NW wave states through LDS
-  if (g == 0) {
-    sm_ml[wid][0][col] = mrow;
-    sm_ml[wid][1][col] = lrow;
-  }
-#pragma unroll
-  for (int j = 0; j < NB; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sm_o[wid][j * 16 + 4 * g + r][col] = o[j][r];
+  sm.store(wid, col, g, mrow, lrow, o);
   __syncthreads();
   for (int idx = tid; idx < G * D; idx += 64 * NW) {
     const int q = idx / D, d = idx - q * D;
-    float M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) M = fmaxf(M, sm_ml[w][0][q]);
-    float L = 0.f, O = 0.f;
-    if (M != -INFINITY) {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        const float e = __builtin_amdgcn_exp2f(sm_ml[w][0][q] - M);
-        L += sm_ml[w][1][q] * e;
-        O += sm_o[w][d][q] * e;
-      }
-    }
+    float M, L, O;
+    sm.reduce(q, d, M, L, O);
     const int h = hk * G + q;
     if (ns == 1) {
       a.o[(int64_t)b * a.o_sb + (int64_t)h * D + d] = f2bf(L > 0.f ? O / L : 0.f);
@@ -608,43 +504,32 @@ hipError_t paged_decode(const DecodeArgs& a, int B, int D, hipStream_t stream) {
   const bool pf = (a.pf[0] != nullptr && a.pf_bytes[0] > 0) || (a.pf[1] != nullptr && a.pf_bytes[1] > 0);
   const int per_z = a.nsplit * a.Hkv;
   const int pfz = pf ? (192 + per_z - 1) / per_z : 0;
-  dim3 grid(a.nsplit, a.Hkv, B + pfz), block(64 * PD_NW);
-#define PD_LAUNCH(D_)                                                                               \
-  do {                                                                                              \
-    if (a.kv_fp8) hipLaunchKernelGGL((paged_decode_kernel<D_, true>), grid, block, 0, stream, a, B);  \
-    else hipLaunchKernelGGL((paged_decode_kernel<D_, false>), grid, block, 0, stream, a, B);          \
-  } while (0)
-  if (D == 64) PD_LAUNCH(64);
-  else if (D == 128) PD_LAUNCH(128);
-  else if (D == 32) PD_LAUNCH(32);
-  else return hipErrorInvalidValue;
-#undef PD_LAUNCH
-  return hipGetLastError();
+  dim3 grid(a.nsplit, a.Hkv, B + pfz), block(64 * PA_NW);
+  const bool ok = pa_dispatch(D, a.kv_fp8, [&](auto d, auto f8) {
+    hipLaunchKernelGGL((paged_decode_kernel<decltype(d)::value, decltype(f8)::value>), grid, block, 0, stream, a, B);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------ paged prefill attention
 // Queries are T new rows of one sequence at positions start_pos.., keys / values are the paged
 // pools read through the sequence's block list (the chunk's own k / v were written by rope_kv
 // before this launch): chunked prefill and prefix reuse without a contiguous copy of the prefix.
-// Same operand scheme as paged_decode (S^T = K Q^T with K rows in the permuted token order,
-// O^T += V^T P^T from the transposed V pool), but the 16 MFMA columns are (query row, head in
+// The block step is paged_decode's (paged_attn.h), but the 16 MFMA columns are (query row, head in
 // group) pairs: column c of a workgroup <-> row c / G, head hk * G + c % G, so a G that does not
 // divide 16 wastes at most G - 1 columns per workgroup.  One workgroup of 4 waves per (tile of
 // 64 / G query rows, kv head); every wave carries all PP_NCT = 4 column tiles and walks blocks
 // wid, wid + 4, ... up to the tile's last position, so each block's K / V fragments are loaded
 // once per workgroup and reused by 64 columns; the 4 wave states merge through LDS, one column
-// tile at a time.  Causal: column at position p sees tokens <= p; their scores go to -inf before
-// the max, V lanes past the sequence end are zeroed (never-written slots may hold NaN).
-constexpr int PP_NW = 4;
+// tile at a time.  Causal: column at position p sees tokens <= p.
 constexpr int PP_NCT = 4;
 
 template <int D, bool F8KV>
-__global__ void __launch_bounds__(64 * PP_NW) paged_prefill_kernel(PrefillArgs a) {
-  constexpr int NW = PP_NW, NCT = PP_NCT;
+__global__ void __launch_bounds__(64 * PA_NW) paged_prefill_kernel(PrefillArgs a) {
+  constexpr int NW = PA_NW, NCT = PP_NCT;
   constexpr int KS = D / 32;   // k-steps of S^T over the head dim
   constexpr int NB = D / 16;   // 16-wide d blocks of O^T
-  __shared__ float sm_ml[NW][2][16];
-  __shared__ float sm_o[NW][D][17];
+  __shared__ WaveMerge<D> sm;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -690,105 +575,18 @@ __global__ void __launch_bounds__(64 * PP_NW) paged_prefill_kernel(PrefillArgs a
   for (int bi = wid; bi < nblk; bi += NW) {
     if (bi != wid) phys = a.blocks[bi];
     phys = min(max(phys, (int64_t)0), (int64_t)a.num_blocks - 1);   // a bad list entry must not leave the pool
-    const int64_t kvo = (phys * a.Hkv + hk) * KV_BLOCK * D;   // elements (= bytes for fp8)
-    const uint16_t* kb = a.k_cache + kvo;
-    const uint16_t* vb = a.v_cache + kvo;
-    const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k_cache) + kvo;
-    const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v_cache) + kvo;
     const int tok0 = bi * KV_BLOCK;
-    const int valid = min(KV_BLOCK, S - tok0);
-
-    // every K and V fragment of the block in flight at once (tile / token order: paged_decode)
     bf16x8_t kf[4][KS];
     bf16x8_t vf[2][NB];
-    const int64_t vro = (int64_t)col * KV_BLOCK + 8 * g;
-#pragma unroll
-    for (int kb16 = 0; kb16 < 4; ++kb16) {
-      const int tok = 32 * (kb16 >> 1) + 8 * (col >> 2) + 4 * (kb16 & 1) + (col & 3);
-#pragma unroll
-      for (int t = 0; t < KS; ++t) {
-        if constexpr (F8KV) {
-          const uint2 w = *(const uint2*)(kb8 + (int64_t)tok * D + g * 8 + t * 32);
-          kf[kb16][t] = __builtin_bit_cast(bf16x8_t, fp8x8_to_bf16(w.x, w.y));
-        } else {
-          kf[kb16][t] = *(const bf16x8_t*)(kb + (int64_t)tok * D + g * 8 + t * 32);
-        }
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        if constexpr (F8KV) {
-          const uint2 w = *(const uint2*)(vb8 + vro + 32 * s + (int64_t)j * 16 * KV_BLOCK);
-          vf[s][j] = __builtin_bit_cast(bf16x8_t, fp8x8_to_bf16(w.x, w.y));
-        } else {
-          vf[s][j] = *(const bf16x8_t*)(vb + vro + 32 * s + (int64_t)j * 16 * KV_BLOCK);
-        }
-      }
-    // slots past the sequence end were never written: no 0 * NaN through the PV MFMA
-    if (valid < KV_BLOCK) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (32 * s + 8 * g + e >= valid) {
-#pragma unroll
-            for (int j = 0; j < NB; ++j) vf[s][j][e] = (__bf16)0.f;
-          }
-    }
-
+    load_kv_block<D, F8KV>(a.k_cache, a.v_cache, (phys * a.Hkv + hk) * KV_BLOCK * D, col, g, kf, vf);
+    zero_v_tail(vf, min(KV_BLOCK, S - tok0), g);
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
       f32x4_t sc[4];
-#pragma unroll
-      for (int kb16 = 0; kb16 < 4; ++kb16) {
-        sc[kb16] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < KS; ++t)
-          sc[kb16] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kb16][t], qf[ct][t], sc[kb16], 0, 0, 0);
-      }
-      const int seen = lim[ct] - tok0;   // tokens of this block the column may see
-      float mx = mrow[ct];
-#pragma unroll
-      for (int kb16 = 0; kb16 < 4; ++kb16)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int tok = 32 * (kb16 >> 1) + 8 * g + 4 * (kb16 & 1) + r;
-          const float sv = tok < seen ? sc[kb16][r] * a.scale_log2 : -INFINITY;
-          sc[kb16][r] = sv;
-          mx = fmaxf(mx, sv);
-        }
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mbase = mx == -INFINITY ? 0.f : mx;
-      const float alpha = __builtin_amdgcn_exp2f(mrow[ct] - mbase);
-      float rs = 0.f;
-#pragma unroll
-      for (int kb16 = 0; kb16 < 4; ++kb16)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = __builtin_amdgcn_exp2f(sc[kb16][r] - mbase);
-          sc[kb16][r] = p;
-          rs += p;
-        }
-      rs += __shfl_xor(rs, 16, 64);
-      rs += __shfl_xor(rs, 32, 64);
-      lrow[ct] = lrow[ct] * alpha + rs;
-      mrow[ct] = mx;
-#pragma unroll
-      for (int j = 0; j < NB; ++j) o[ct][j] *= alpha;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8_t pf;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          pf[r] = (__bf16)sc[2 * s][r];
-          pf[4 + r] = (__bf16)sc[2 * s + 1][r];
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) o[ct][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[s][j], pf, o[ct][j], 0, 0, 0);
-      }
+      qk_scores(kf, qf[ct], sc);
+      // the column sees lim[ct] - tok0 tokens of this block
+      softmax_step(sc, lim[ct] - tok0, a.scale_log2, g, mrow[ct], lrow[ct], o[ct]);
+      pv_step(sc, vf, o[ct]);
     }
   }
 
@@ -796,32 +594,15 @@ __global__ void __launch_bounds__(64 * PP_NW) paged_prefill_kernel(PrefillArgs a
 #pragma unroll
   for (int ct = 0; ct < NCT; ++ct) {
     if (ct > 0) __syncthreads();
-    if (g == 0) {
-      sm_ml[wid][0][col] = mrow[ct];
-      sm_ml[wid][1][col] = lrow[ct];
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sm_o[wid][j * 16 + 4 * g + r][col] = o[ct][j][r];
+    sm.store(wid, col, g, mrow[ct], lrow[ct], o[ct]);
     __syncthreads();
     for (int idx = tid; idx < 16 * D; idx += 64 * NW) {
       const int qc = idx / D, d = idx - qc * D;
       const int c = ct * 16 + qc;
       const int rl = c / G, hg = c - rl * G;
       if (rl >= rows) continue;
-      float M = -INFINITY;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) M = fmaxf(M, sm_ml[w][0][qc]);
-      float L = 0.f, O = 0.f;
-      if (M != -INFINITY) {
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-          const float e = __builtin_amdgcn_exp2f(sm_ml[w][0][qc] - M);
-          L += sm_ml[w][1][qc] * e;
-          O += sm_o[w][d][qc] * e;
-        }
-      }
+      float M, L, O;
+      sm.reduce(qc, d, M, L, O);
       a.o[(int64_t)(row0 + rl) * a.o_ld + (int64_t)(hk * G + hg) * D + d] = f2bf(L > 0.f ? O / L : 0.f);
     }
   }
@@ -831,18 +612,11 @@ hipError_t paged_prefill(const PrefillArgs& a, int D, hipStream_t stream) {
   if (a.T <= 0) return hipSuccess;
   if (a.Hkv <= 0 || a.H % a.Hkv != 0 || a.H / a.Hkv > 16 || a.num_blocks <= 0 || a.start_pos < 0) return hipErrorInvalidValue;
   const int QT = (16 * PP_NCT) / (a.H / a.Hkv);
-  dim3 grid((a.T + QT - 1) / QT, a.Hkv), block(64 * PP_NW);
-#define PP_LAUNCH(D_)                                                                            \
-  do {                                                                                           \
-    if (a.kv_fp8) hipLaunchKernelGGL((paged_prefill_kernel<D_, true>), grid, block, 0, stream, a); \
-    else hipLaunchKernelGGL((paged_prefill_kernel<D_, false>), grid, block, 0, stream, a);         \
-  } while (0)
-  if (D == 64) PP_LAUNCH(64);
-  else if (D == 128) PP_LAUNCH(128);
-  else if (D == 32) PP_LAUNCH(32);
-  else return hipErrorInvalidValue;
-#undef PP_LAUNCH
-  return hipGetLastError();
+  dim3 grid((a.T + QT - 1) / QT, a.Hkv), block(64 * PA_NW);
+  const bool ok = pa_dispatch(D, a.kv_fp8, [&](auto d, auto f8) {
+    hipLaunchKernelGGL((paged_prefill_kernel<decltype(d)::value, decltype(f8)::value>), grid, block, 0, stream, a);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------ repetition penalty

@@ -80,11 +80,22 @@ def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, cos_sin: torch.Tensor, H: int,
             v_cache[blk, :, :, off] = vt.to(v_cache.dtype)
 
 
-_DECODE_WAVES = 4             # waves (= 64-token blocks) per paged-decode workgroup (csrc/llm.hip PD_NW)
+def gather_kv(k_cache: torch.Tensor, v_cache: torch.Tensor, blocks: torch.Tensor,
+              n_tokens: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """Token-major K and V [n_tokens, Hkv, D] of the sequence whose block list is ``blocks``
+    (int64, >= ceil(n_tokens / 64) entries), copied out of the pools in the cache's dtype."""
+    Hkv, D = k_cache.shape[1], k_cache.shape[3]
+    kb = k_cache.index_select(0, blocks)                                  # [nb, Hkv, 64, D]
+    vb = v_cache.index_select(0, blocks)                                  # [nb, Hkv, D, 64]
+    return (kb.permute(0, 2, 1, 3).reshape(-1, Hkv, D)[:n_tokens],
+            vb.permute(0, 3, 1, 2).reshape(-1, Hkv, D)[:n_tokens])
+
+
+_DECODE_WAVES = 4            # waves (= 64-token blocks) per paged-decode workgroup (csrc/paged_attn.h PA_NW)
 _DECODE_MAX_SPLITS = 32        # the in-launch split combine merges at most 32 splits per kv head
 
 
-_DECODE_FEW = 4                # <= this many sequences: one-wave workgroups, one block per split
+_DECODE_FEW = 4                # <= this many sequences: no minimum split size, blocks spread over every split
 
 
 def decode_splits(B: int, Hkv: int, max_blocks: int, target_wg: Optional[int] = None) -> tuple[int, int]:
@@ -155,10 +166,8 @@ def paged_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     G = H // Hkv
     for b in range(B):
         L = int(ctx_len[b])
-        nb = -(-L // KV_BLOCK)
-        blocks = block_table[b, :nb].long()
-        k = k_cache[blocks].float().permute(1, 0, 2, 3).reshape(Hkv, nb * KV_BLOCK, D)[:, :L]
-        v = v_cache[blocks].float().permute(1, 0, 3, 2).reshape(Hkv, nb * KV_BLOCK, D)[:, :L]
+        k, v = gather_kv(k_cache, v_cache, block_table[b, :-(-L // KV_BLOCK)].long(), L)
+        k, v = k.float().permute(1, 0, 2), v.float().permute(1, 0, 2)          # [Hkv, L, D]
         qb = q[b, :H * D].float().view(Hkv, G, D)
         s = torch.einsum("hgd,htd->hgt", qb, k) * scale
         p = torch.softmax(s, -1)
@@ -193,9 +202,8 @@ def paged_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     nb = -(-S // KV_BLOCK)
     if blocks.numel() < nb:
         raise ValueError("paged_prefill: block list shorter than start_pos + T")
-    bl = blocks[:nb].long()
-    k = k_cache[bl].float().permute(1, 0, 2, 3).reshape(Hkv, nb * KV_BLOCK, D)[:, :S]
-    v = v_cache[bl].float().permute(1, 0, 3, 2).reshape(Hkv, nb * KV_BLOCK, D)[:, :S]
+    k, v = gather_kv(k_cache, v_cache, blocks[:nb].long(), S)
+    k, v = k.float().permute(1, 0, 2), v.float().permute(1, 0, 2)              # [Hkv, S, D]
     qb = q[:, :H * D].float().view(T, Hkv, G, D)
     s = torch.einsum("thgd,hsd->hgts", qb, k) * scale
     hidden = torch.arange(S)[None, :] > (start_pos + torch.arange(T))[:, None]       # [T, S]

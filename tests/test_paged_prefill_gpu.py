@@ -54,7 +54,7 @@ def _rows(qbuf):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, FP8], ids=["bf16", "fp8"])
 @pytest.mark.parametrize("start,T", [(0, 70), (64, 1), (64, 17), (100, 130), (577, 47)])
-@pytest.mark.parametrize("H,Hkv,D", [(14, 2, 64), (32, 8, 128), (4, 4, 64), (16, 1, 64)])
+@pytest.mark.parametrize("H,Hkv,D", [(14, 2, 64), (32, 8, 128), (4, 4, 64), (16, 1, 64), (4, 2, 32)])
 def test_paged_prefill_vs_cpu_reference(H, Hkv, D, start, T, dtype):
     qbuf, kc, vc, blocks = _case(H, Hkv, D, start, T, dtype, seed=H * D + start + T)
     assert not torch.isfinite(kc.float()).all() and not torch.isfinite(vc.float()).all()   # the NaN slots are there

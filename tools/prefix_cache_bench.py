@@ -10,7 +10,7 @@ Mirrors tools/vlm_bench.py (random-weight LLaVA-Llama-3-8B preset, fp8 weights, 
  (b) the host time of hashing the JPEG and building the block keys (paid by every request when
      the cache is on);
  (c) the paged-prefill kernel against the gather path (LUMEN_PAGED_PREFILL=0: index_select of
-     the prefix, widening copy, transposing copy, flash kernel) for one 8B layer shape
+     the prefix, transposing copy, widening copy, flash kernel) for one 8B layer shape
      (H=32, Hkv=8, D=128), bf16 and fp8 caches, cache-cold (every call reads a block set the
      previous calls did not touch; the pools are larger than the Infinity Cache).
 
@@ -51,12 +51,9 @@ def gather_attention(qkv, kc, vc, blocks, start_pos, H, Hkv, D):
     T = qkv.shape[0]
     S = start_pos + T
     q5 = qkv.view(1, T, H + 2 * Hkv, D)
-    kb = kc.index_select(0, blocks)
-    vb = vc.index_select(0, blocks)
-    if kb.dtype != qkv.dtype:
-        kb, vb = kb.to(qkv.dtype), vb.to(qkv.dtype)
-    k_all = kb.permute(0, 2, 1, 3).reshape(1, -1, Hkv, D)[:, :S]
-    v_all = vb.permute(0, 3, 1, 2).reshape(1, -1, Hkv, D)[:, :S].contiguous()
+    k_all, v_all = lops.gather_kv(kc, vc, blocks, S)
+    k_all = k_all.to(qkv.dtype).unsqueeze(0)
+    v_all = v_all.to(qkv.dtype).unsqueeze(0).contiguous()
     return ops.attention(q5[:, :, :H], k_all, v_all, causal=True).view(T, H * D)
 
 
