@@ -18,6 +18,7 @@
 
 #include "gemm_epi.h"
 #include "attention.h"
+#include "pooled_attn.h"
 #include "tuning.h"
 #include "conv.h"
 #include "gemm_w4.h"
@@ -776,6 +777,49 @@ void attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, at
   LM_CHECK_HIP(lumen::attn_fwd(a, (int)B, (int)D, cur_stream()));
 }
 
+// pooled-query attention over the residual stream (pooled_attn.hip): x [B*S, W] bf16, st [B*S, 2] fp32,
+// g [B, H, W] bf16, s [B, H] fp32 -> z [B*H, W] bf16, c [B*H] fp32
+void pooled_attention_x(const at::Tensor& x, const at::Tensor& st, const at::Tensor& g, const at::Tensor& s,
+                        const c10::optional<at::Tensor>& kv_len, at::Tensor z, at::Tensor c, int64_t S) {
+  check_bf16_rows(x, "x");
+  const int64_t W = x.size(1);
+  TORCH_CHECK(S >= 1 && x.size(0) % S == 0, "pooled_attention_x: x [B*S, W]");
+  const int64_t B = x.size(0) / S;
+  check_gpu(g, "g");
+  TORCH_CHECK(g.scalar_type() == at::kBFloat16 && g.dim() == 3 && g.is_contiguous() && g.size(0) == B &&
+                  g.size(2) == W && (reinterpret_cast<uintptr_t>(g.data_ptr()) % 16) == 0,
+              "pooled_attention_x: g must be contiguous bf16 [B, H, W]");
+  const int64_t H = g.size(1);
+  TORCH_CHECK(W % 64 == 0 && (W <= 1024 || (W % 128 == 0 && W <= 2048)) && H >= 1,
+              "pooled_attention_x: W % 64 == 0, W <= 1024 (W % 128 == 0: <= 2048)");
+  TORCH_CHECK(st.is_cuda() && st.scalar_type() == at::kFloat && st.is_contiguous() && st.numel() == 2 * B * S,
+              "pooled_attention_x: st must be fp32 [B*S, 2]");
+  TORCH_CHECK(s.is_cuda() && s.scalar_type() == at::kFloat && s.is_contiguous() && s.numel() == B * H,
+              "pooled_attention_x: s must be fp32 [B, H]");
+  check_bf16_rows(z, "z");
+  TORCH_CHECK(z.is_contiguous() && z.size(0) == B * H && z.size(1) == W, "pooled_attention_x: z bf16 [B*H, W]");
+  TORCH_CHECK(c.is_cuda() && c.scalar_type() == at::kFloat && c.is_contiguous() && c.numel() == B * H,
+              "pooled_attention_x: c must be fp32 [B*H]");
+  for (const at::Tensor& t : {st, g, s, z, c})
+    TORCH_CHECK(t.device() == x.device(), "pooled_attention_x: every tensor must be on x's device");
+  lumen::PooledAttnArgs a{};
+  a.x = bf(x); a.ldx = x.stride(0);
+  a.st = st.data_ptr<float>();
+  a.g = bf(g);
+  a.s = s.data_ptr<float>();
+  if (kv_len.has_value() && kv_len->defined()) {
+    TORCH_CHECK(kv_len->is_cuda() && kv_len->scalar_type() == at::kInt && kv_len->is_contiguous() &&
+                    kv_len->numel() == B && kv_len->device() == x.device(),
+                "pooled_attention_x: kv_len int32 [B] on x's device");
+    a.kv_len = kv_len->data_ptr<int>();
+  }
+  a.z = bfm(z);
+  a.c = c.data_ptr<float>();
+  a.S = (int)S; a.W = (int)W; a.H = (int)H;
+  const at::DeviceGuard guard(x.device());
+  LM_CHECK_HIP(lumen::pooled_attn_x(a, (int)B, cur_stream()));
+}
+
 // attention with an MX fp8 output (the W8A8 o-projection's operand): o8 e4m3fn [B, Sq, H*D] (or
 // [Sq, H*D] when B == 1), os uint8 scale planes [B, H*D/128, Sq, 4] (or 3-D when B == 1); o (bf16
 // [B, Sq, H, D]) optional.
@@ -1130,6 +1174,8 @@ TORCH_LIBRARY(lumen, m) {
   m.def("attention(Tensor q, Tensor k, Tensor v, Tensor(o!) o, Tensor? kv_len, float scale, bool causal) -> ()");
   m.def("attention_mx(Tensor q, Tensor k, Tensor v, Tensor(o!)? o, Tensor(q8!) o8, Tensor(s!) os, Tensor? kv_len, "
         "float scale, bool causal) -> ()");
+  m.def("pooled_attention_x(Tensor x, Tensor st, Tensor g, Tensor s, Tensor? kv_len, Tensor(z!) z, Tensor(c!) c, "
+        "int seq) -> ()");
   m.def("image_prep(Tensor src, Tensor geom, Tensor(o!) out, Tensor(t!) tmp, int out_h, int out_w, int filter, "
         "bool swap_rb, float[] mean, float[] std, float scale, float pad, int layout, int patch, int kpad, "
         "int max_ch, int max_dw) -> ()");
@@ -1171,6 +1217,7 @@ TORCH_LIBRARY_IMPL(lumen, CUDA, m) {
   m.impl("embed_gather", &embed_gather);
   m.impl("attention", &attention);
   m.impl("attention_mx", &attention_mx);
+  m.impl("pooled_attention_x", &pooled_attention_x);
   m.impl("image_prep", &image_prep2);
   m.impl("image_prep_band", &image_prep_band);
   m.impl("row_topk", &row_topk);

@@ -4,11 +4,18 @@ The towers are written directly against :mod:`lumen_amd.ops`, i.e. every hot op
 is one hand-written gfx950 kernel on the GPU:
 
   image_prep (resize+normalise+im2col)  -> patch GEMM (epilogue: +pos-emb, row
-  scatter into the token buffer) -> cls_fill -> ln_pre -> L x [LN -> QKV GEMM ->
+  scatter into the token buffer) -> cls_fill -> ln_pre -> (L - 1) x [LN -> QKV GEMM ->
   fused attention (reads the packed QKV in place) -> out-proj GEMM (+bias
   +residual in place) -> LN -> fc1 GEMM (+bias, GELU/QuickGELU) -> fc2 GEMM (+bias
-  +residual)] -> ln_post on CLS rows (row gather) -> projection GEMM (fp32 out) ->
-  L2 normalise.
+  +residual)] -> pooled final block -> ln_post -> projection GEMM (fp32 out) -> L2 normalise.
+
+The embedding only reads the CLS row (text: the EOT row) of the last block, and the other rows of
+that block only feed its K and V, so the last block runs for the B pooled rows alone
+(_pooled_final_block): row statistics of x -> Q of the pooled rows -> the query pushed through the
+LN-folded K weights (one GEMM over B x heads rows) -> pooled-query attention over the raw residual rows
+(ops.pooled_attention_x: one streaming read of x, K and V are never formed) -> LN-folded V weights
+(B x heads rows) -> out-proj, LN statistics, fc1, fc2 on B rows.  forward_features (LLaVA hidden layer
+-2) keeps every row of every block.
 
 Reference behaviour reproduced: image embedding = normalised projection of the
 CLS token (packages/lumen-clip/src/lumen_clip/backends/onnxrt_backend.py:466-495,
@@ -200,6 +207,18 @@ class _Block(nn.Module):
             self._lnf_cache = (qw, qa, fw, fa)
             self._lnf_key = key
         return self._lnf_cache
+
+    def lnf_pooled(self):
+        """What the pooled final block (:func:`_pooled_final_block`) needs beside :meth:`lnf`, cached
+        under the same key: (q col_aff [2, W], the folded K weights transposed [W in, W out] -- the GEMM
+        that pushes the pooled query through them reads them as its [N, K] weight -- and v col_aff [2, W])."""
+        qw, qa, _, _ = self.lnf()
+        if getattr(self, "_lnfp_key", None) != self._lnf_key:
+            W = qw.shape[1]
+            with torch.no_grad():
+                self._lnfp_cache = (qa[:, :W].contiguous(), qw[W:2 * W].t().contiguous(), qa[:, 2 * W:].contiguous())
+            self._lnfp_key = self._lnf_key
+        return self._lnfp_cache
 
     def mx_weights(self) -> dict:
         """W8A8 form for the MX tower chain (run_blocks_mx): OCP e4m3 weights with per-output-channel
@@ -448,6 +467,64 @@ def run_blocks(x: torch.Tensor, blocks, B: int, S: int, heads: int, act: str, ep
     return x
 
 
+def _pooled_final_block(x: torch.Tensor, blk: "_Block", B: int, S: int, heads: int, act: str, eps: float,
+                        q_rows: Optional[torch.Tensor] = None, kv_len: Optional[torch.Tensor] = None,
+                        fold: Optional[bool] = None) -> torch.Tensor:
+    """The output of pre-LN block ``blk`` over x [B*S, W] at ONE row per sequence (position ``q_rows`` [B],
+    default 0), as [B, W]: what a tower's last block owes a pooled embedding.  The other rows of that
+    block only feed its K and V, so Q, attention, out-projection and the MLP run on B rows; ``kv_len``
+    [B] = the keys the pooled row attends to (text: eot + 1, i.e. its causal row).  x is not modified.
+
+    ``fold`` (the GPU form): K and V are not formed either.  With n_j = LN1(x_j) and the LayerNorm
+    folded into the weights (:meth:`_Block.lnf`), the score of head h is n_j . u_h + const_h for
+    u_h = scale * q_h . Wk_h -- the K bias and the LN beta add a per-head constant that the softmax
+    drops -- and the head output is (sum_j p_hj n_j) . Wv_h^T + bv_h.  Both sides are taken over the
+    raw rows x_j in one pass (ops.pooled_attention_x), followed by GEMMs over B * heads rows.
+    Otherwise (CPU): K / V of all rows and ops.attention with one query row."""
+    T, W = x.shape
+    D = W // heads
+    dev = x.device
+    fold = x.is_cuda if fold is None else fold
+    rows = torch.arange(B, device=dev, dtype=torch.long) * S
+    if q_rows is not None:
+        rows = rows + q_rows.to(dev).long()
+    xq = x.index_select(0, rows)
+    if fold:
+        qw, _, fw, fa = blk.lnf()
+        q_aff, kwt, v_aff = blk.lnf_pooled()
+        st = ops.ln_row_stats(x, eps)
+        q = ops.linear_lnf(xq, qw[:W], q_aff, st.index_select(0, rows))
+        # g[b, h] = scale * q_h . Wk'_h as ONE GEMM: row (b, h) carries q_h in head h's D columns, zeros elsewhere
+        qx = torch.zeros((B, heads, heads, D), device=dev, dtype=x.dtype)
+        qx.diagonal(dim1=1, dim2=2).copy_(q.view(B, heads, D).permute(0, 2, 1))
+        g = ops.linear(qx.view(B * heads, W), kwt, alpha=D ** -0.5)
+        z, c = ops.pooled_attention_x(x, st, g.view(B, heads, W), g.float().sum(-1).view(B, heads), S, kv_len)
+        # row (b, h) of LN-folded V over (z, c): every head's columns; head h's own D are its output
+        v = ops.linear_lnf(z, qw[2 * W:], v_aff, torch.stack([torch.ones_like(c), c], dim=1))
+        o = v.view(B, heads, heads, D).diagonal(dim1=1, dim2=2).permute(0, 2, 1).reshape(B, W)
+    else:
+        h = ops.layer_norm(x, blk.ln1_w, blk.ln1_b, eps)
+        qkv = ops.linear(h, blk.qkv_w, blk.qkv_b)
+        q = qkv.index_select(0, rows)[:, :W].reshape(B, 1, heads, D)
+        q5 = qkv.view(B, S, 3, heads, D)
+        o = ops.attention(q, q5[:, :, 1], q5[:, :, 2], kv_len=kv_len).reshape(B, W)
+    y = ops.linear(o, blk.out_w, blk.out_b, residual=xq)
+    if fold:
+        f = ops.linear_lnf(y, fw, fa, ops.ln_row_stats(y, eps), act=act)
+    else:
+        f = ops.linear(ops.layer_norm(y, blk.ln2_w, blk.ln2_b, eps), blk.fc1_w, blk.fc1_b, act=act)
+    return ops.linear(f, blk.fc2_w, blk.fc2_b, residual=y)
+
+
+def _pooled_final_ok(x: torch.Tensor, blocks, heads: int, S: int) -> bool:
+    """Whether the tower's last block runs as :func:`_pooled_final_block` (else as a full block)."""
+    if not _POOLED_FINAL or len(blocks) == 0:
+        return False
+    if not x.is_cuda:
+        return True
+    return _LN_FOLD and x.shape[0] >= _POOLED_FINAL_MIN_ROWS and ops.pooled_attention_ok(x.shape[1], heads, S)
+
+
 # Micro-batched tower (large image batches on the GPU): the batch is cut into LUMEN_VIT_MICRO
 # row ranges, each issued on its own HIP stream, layer-interleaved.  A 256x256-tile GEMM over
 # M = B*257 rows ends on a nearly empty round of tiles (ViT-L/14 b512: 514 row tiles); with two
@@ -460,6 +537,14 @@ _VIT_MICRO = int(os.environ.get("LUMEN_VIT_MICRO", "2"))
 # batch loops, profiles/r5_clip_graph_serve_v1.txt -- and was removed in r6)
 log = logging.getLogger(__name__)
 _LN_FOLD = True   # GPU blocks: LayerNorms folded into qkv / fc1 (see _block_steps)
+# the last block of the pooled towers (image CLS / text EOT embeddings) runs for the pooled rows only, its
+# attention over the raw residual rows (_pooled_final_block); forward_features keeps every row of every block
+_POOLED_FINAL = True
+# ... on the GPU from this many token rows.  The pooled tail is ~20 small launches, latency-bound at any batch,
+# against one full block's 7: below the threshold it loses (ViT-L/14 b1 / b4 / b8: +2.2 / +1.2 / +0.6 % step time,
+# ViT-B/32 b64 = 3,200 rows: +2.4 %), above it wins (ViT-L/14 b16 = 4,112 rows: -1.3 %, b24: -1.6 %, ViT-B/32
+# b160 = 8,000 rows: -2.2 %; profiles/pooled_final_block_v1.txt), so single-request serving keeps the full block
+_POOLED_FINAL_MIN_ROWS = 4096
 # (r5's LayerNorm partials from the residual GEMMs -- no gain: the row-statistics pass already hides behind
 # the other stream's GEMMs, 6248 vs 6251-6268 img/s, profiles/r5_gemm_pp_ds_v1.txt -- were removed in r6)
 # ping-pong 256x256, 2 phases per K-tile + priority, no tail split (r2: group_m 2 = 1629 vs 1609 / 1689:
@@ -580,9 +665,17 @@ class VisionTower(nn.Module):
                    out_group=P, out_group_stride=S, out_row_offset=1)
         ops.cls_fill(x, self.class_emb, self.pos_emb, S)
         ops.layer_norm(x, self.ln_pre_w, self.ln_pre_b, cfg.ln_eps, out=x)
-        run_blocks_micro(x, self.blocks, B, S, cfg.heads, cfg.act, cfg.ln_eps)
-        cls_rows = torch.arange(B, device=dev, dtype=torch.long) * S
-        pooled = ops.layer_norm(x, self.ln_post_w, self.ln_post_b, cfg.ln_eps, row_idx=cls_rows)
+        if _pooled_final_ok(x, self.blocks, cfg.heads, S):
+            # blocks 1 .. L-1 over every row (micro-batched), then, after the join on the caller's stream,
+            # the last block for the CLS rows only
+            if len(self.blocks) > 1:
+                run_blocks_micro(x, self.blocks[:-1], B, S, cfg.heads, cfg.act, cfg.ln_eps)
+            cls = _pooled_final_block(x, self.blocks[-1], B, S, cfg.heads, cfg.act, cfg.ln_eps)
+            pooled = ops.layer_norm(cls, self.ln_post_w, self.ln_post_b, cfg.ln_eps)
+        else:
+            run_blocks_micro(x, self.blocks, B, S, cfg.heads, cfg.act, cfg.ln_eps)
+            cls_rows = torch.arange(B, device=dev, dtype=torch.long) * S
+            pooled = ops.layer_norm(x, self.ln_post_w, self.ln_post_b, cfg.ln_eps, row_idx=cls_rows)
         emb = ops.linear(pooled, self.proj_w, out_dtype=torch.float32)
         return ops.l2_normalize_(emb)
 
@@ -664,14 +757,23 @@ class TextTower(nn.Module):
         dev = self.token_emb.device
         ids = ids.to(dev)
         x = ops.embed(ids, self.token_emb, self.pos_emb[:S]).view(B * S, cfg.width)
-        run_blocks_micro(x, self.blocks, B, S, cfg.heads, cfg.act, cfg.ln_eps, causal=True,
-                         min_rows=_TEXT_MICRO_MIN_ROWS, tile=-1, res_tile=-1)
         if cfg.eot_token_id is None:
             eot = ids.argmax(dim=-1)
         else:
             eot = (ids == cfg.eot_token_id).int().argmax(dim=-1)
-        rows = torch.arange(B, device=dev) * S + eot
-        pooled = ops.layer_norm(x, self.ln_final_w, self.ln_final_b, cfg.ln_eps, row_idx=rows.long())
+        if _pooled_final_ok(x, self.blocks, cfg.heads, S):
+            # the last block for the EOT rows only: causal attention of one row = keys [0, eot]
+            if len(self.blocks) > 1:
+                run_blocks_micro(x, self.blocks[:-1], B, S, cfg.heads, cfg.act, cfg.ln_eps, causal=True,
+                                 min_rows=_TEXT_MICRO_MIN_ROWS, tile=-1, res_tile=-1)
+            last = _pooled_final_block(x, self.blocks[-1], B, S, cfg.heads, cfg.act, cfg.ln_eps, q_rows=eot,
+                                       kv_len=(eot + 1).to(torch.int32))
+            pooled = ops.layer_norm(last, self.ln_final_w, self.ln_final_b, cfg.ln_eps)
+        else:
+            run_blocks_micro(x, self.blocks, B, S, cfg.heads, cfg.act, cfg.ln_eps, causal=True,
+                             min_rows=_TEXT_MICRO_MIN_ROWS, tile=-1, res_tile=-1)
+            rows = torch.arange(B, device=dev) * S + eot
+            pooled = ops.layer_norm(x, self.ln_final_w, self.ln_final_b, cfg.ln_eps, row_idx=rows.long())
         emb = ops.linear(pooled, self.proj_w, out_dtype=torch.float32)
         return ops.l2_normalize_(emb)
 

@@ -681,6 +681,51 @@ def attention_mx(q, k, v, scale: Optional[float] = None, causal: bool = False, k
     return o8, os_
 
 
+def pooled_attention_ok(W: int, heads: int, S: int) -> bool:
+    """Shapes :func:`pooled_attention_x` takes on the GPU: width a multiple of 64 (up to 1024, or up to 2048
+    in multiples of 128: at most 16 waves of 64 / 128 columns), head dim 32 / 64 / 128, S <= 1024."""
+    if heads <= 0 or W % heads or W // heads not in (32, 64, 128) or not 1 <= S <= 1024:
+        return False
+    return W % 64 == 0 and (W <= 1024 or (W % 128 == 0 and W <= 2048))
+
+
+def pooled_attention_x(x: torch.Tensor, st: torch.Tensor, g: torch.Tensor, s: torch.Tensor, S: int,
+                       kv_len: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Attention of ONE query per sequence taken over the raw residual rows (csrc/pooled_attn.hip): the
+    query arrives pushed through the LayerNorm-folded K weights, so K and V are never formed.
+
+    x [B*S, W]; st [B*S, 2] fp32 = (rstd, -mean * rstd) (:func:`ln_row_stats`; (1, 0) for rows that are
+    already normalised); g [B, H, W] = scale * q_h . Wk'_h; s [B, H] fp32 = the row sums of g as stored;
+    ``kv_len`` int32 [B] = keys [0, kv_len[b]) (default all S).  Per sequence b and head h:
+
+      score[h, j] = st[j, 0] * (x_j . g[b, h]) + st[j, 1] * s[b, h],   p[h] = softmax_j(score[h])
+      z[b, h]     = sum_j p[h, j] * st[j, 0] * x_j  (W values),        c[b, h] = sum_j p[h, j] * st[j, 1]
+
+    Returns (z [B*H, W] in x's dtype, c [B*H] fp32)."""
+    T, W = x.shape
+    B, H = g.shape[0], g.shape[1]
+    assert T == B * S and g.shape[2] == W, "pooled_attention_x: x [B*S, W], g [B, H, W]"
+    z = torch.empty((B * H, W), device=x.device, dtype=x.dtype)
+    c = torch.empty((B * H,), device=x.device, dtype=torch.float32)
+    if x.is_cuda:
+        if x.stride(-1) != 1 or x.stride(0) % 8 != 0:
+            x = x.contiguous()
+        kl = kv_len.to(torch.int32).contiguous() if kv_len is not None else None
+        hip_ops().pooled_attention_x(x, st, g.contiguous(), s.contiguous(), kl, z, c, int(S))
+        return z, c
+    xf = x.float().view(B, S, W)
+    st3 = st.float().view(B, S, 2)
+    r, t = st3[..., 0][:, None, :], st3[..., 1][:, None, :]                   # [B, 1, S]
+    score = r * torch.einsum("bsw,bhw->bhs", xf, g.float()) + t * s.float().view(B, H, 1)
+    if kv_len is not None:
+        dead = torch.arange(S).view(1, 1, S) >= kv_len.long().view(B, 1, 1)
+        score = score.masked_fill(dead, float("-inf"))
+    p = torch.nan_to_num(torch.softmax(score, dim=-1), nan=0.0)
+    z.copy_(torch.einsum("bhs,bsw->bhw", p * r, xf).reshape(B * H, W).to(z.dtype))
+    c.copy_((p * t).sum(-1).reshape(B * H))
+    return z, c
+
+
 # --------------------------------------------------------------------------- top-k
 def row_topk(scores: torch.Tensor, k: int, scale: float = 1.0, with_lse: bool = False, index_offset: int = 0):
     """Per-row top-k (descending) of fp32 scores [B, N]; optionally the row logsumexp(scale*s).

@@ -56,7 +56,7 @@ def main():
     res = {k: [] for k in arms}
     outs = {}
     for r in range(args.rounds + 1):
-        for name, val in arms.items():
+        for arm, val in arms.items():     # (not `name`: setter() closes over the flag's name)
             setter(val)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -65,8 +65,8 @@ def main():
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             if r > 0:                                   # round 0 = warm-up of both arms
-                res[name].append(args.batch * args.steps / dt)
-            outs[name] = e.float().cpu()
+                res[arm].append(args.batch * args.steps / dt)
+            outs[arm] = e.float().cpu()
     setter(base)
     o1, o2 = (outs[k] for k in arms)
     cos = float((o1 * o2).sum(-1).min())
