@@ -7,6 +7,7 @@
 #include <torch/library.h>
 
 #include "llm.h"
+#include "sampler.h"
 
 namespace lumen {
 uint32_t* splitk_counters(const at::Tensor& like, int64_t tiles);   // ops.cpp
@@ -190,6 +191,61 @@ void rep_penalty_(at::Tensor logits, const at::Tensor& ids, const at::Tensor& pe
                                 penalty.data_ptr<float>(), (int)B, (int)logits.size(1), cur()));
 }
 
+// The in-graph sampler (sampler.hip): per row of logits f32 [B, V] (never written) the repetition
+// penalty over the row's seen-bitmap slot, 1/T, the top-64 candidates, the nucleus cut and the draw
+// with the uniform u.  Writes tok int32 [B] and out_ids int64 [B] (may alias in_ids), marks
+// in_ids[b] in seen[seen_slot[b]]; out_v / out_i [B, 64] and out_lse [B] are optional.
+void sample_rows(const at::Tensor& logits, const at::Tensor& inv_t, const at::Tensor& top_p, const at::Tensor& penalty,
+                 const at::Tensor& u, const at::Tensor& greedy, const at::Tensor& seen_slot, at::Tensor seen,
+                 const at::Tensor& in_ids, at::Tensor out_ids, at::Tensor tok, const c10::optional<at::Tensor>& out_v,
+                 const c10::optional<at::Tensor>& out_i, const c10::optional<at::Tensor>& out_lse) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat && logits.dim() == 2 && logits.stride(1) == 1,
+              "sample_rows: logits f32 [B, V]");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= lumen::SAMPLE_K && V < (int64_t(1) << 31), "sample_rows: V >= 64");
+  auto row = [&](const at::Tensor& t, at::ScalarType ty, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == ty && t.is_contiguous() && t.numel() == B, "sample_rows: ", what);
+  };
+  row(inv_t, at::kFloat, "inv_t f32 [B]");
+  row(top_p, at::kDouble, "top_p f64 [B]");
+  row(penalty, at::kFloat, "penalty f32 [B]");
+  row(u, at::kDouble, "u f64 [B]");
+  row(greedy, at::kInt, "greedy int32 [B]");
+  row(seen_slot, at::kInt, "seen_slot int32 [B]");
+  row(in_ids, at::kLong, "in_ids int64 [B]");
+  row(out_ids, at::kLong, "out_ids int64 [B]");
+  row(tok, at::kInt, "tok int32 [B]");
+  const int64_t words = (V + 31) / 32;
+  TORCH_CHECK(seen.is_cuda() && seen.scalar_type() == at::kInt && seen.is_contiguous() && seen.dim() == 2 &&
+              seen.size(1) == words, "sample_rows: seen int32 [S, ceil(V / 32)]");
+  lumen::SampleArgs a{};
+  a.logits = logits.data_ptr<float>(); a.ld = logits.stride(0);
+  a.B = (int)B; a.V = (int)V;
+  a.inv_t = inv_t.data_ptr<float>(); a.top_p = top_p.data_ptr<double>(); a.penalty = penalty.data_ptr<float>();
+  a.u = u.data_ptr<double>(); a.greedy = greedy.data_ptr<int>(); a.seen_slot = seen_slot.data_ptr<int>();
+  a.seen = seen.data_ptr<int>(); a.S = (int)seen.size(0); a.words = (int)words;
+  a.in_ids = in_ids.data_ptr<int64_t>(); a.out_ids = out_ids.data_ptr<int64_t>(); a.tok = tok.data_ptr<int>();
+  const bool cand = out_v.has_value() && out_v->defined();
+  TORCH_CHECK(cand == (out_i.has_value() && out_i->defined()), "sample_rows: out_v and out_i come together");
+  if (cand) {
+    TORCH_CHECK(out_v->is_cuda() && out_v->scalar_type() == at::kFloat && out_v->is_contiguous() &&
+                out_v->numel() == B * lumen::SAMPLE_K, "sample_rows: out_v f32 [B, 64]");
+    TORCH_CHECK(out_i->is_cuda() && out_i->scalar_type() == at::kInt && out_i->is_contiguous() &&
+                out_i->numel() == B * lumen::SAMPLE_K, "sample_rows: out_i int32 [B, 64]");
+    a.out_v = out_v->data_ptr<float>(); a.out_i = out_i->data_ptr<int>();
+  }
+  if (out_lse.has_value() && out_lse->defined()) {
+    TORCH_CHECK(out_lse->is_cuda() && out_lse->scalar_type() == at::kFloat && out_lse->numel() == B &&
+                out_lse->is_contiguous(), "sample_rows: out_lse f32 [B]");
+    a.out_lse = out_lse->data_ptr<float>();
+  }
+  const at::DeviceGuard g(logits.device());
+  const int64_t nws = lumen::sample_ws_floats((int)B, (int)V);
+  at::Tensor ws;
+  if (nws > 0) ws = at::empty({nws}, logits.options());
+  CHECK_HIP3(lumen::sample_rows(a, nws > 0 ? ws.data_ptr<float>() : nullptr, cur()));
+}
+
 // int32 CPU values -> int64 device tensor through the kernel arguments (llm.hip:upload_i64)
 void upload_small(const at::Tensor& src, at::Tensor out) {
   TORCH_CHECK(!src.is_cuda() && src.scalar_type() == at::kInt && src.is_contiguous(), "upload_small: src int32 CPU");
@@ -216,6 +272,9 @@ TORCH_LIBRARY_FRAGMENT(lumen, m) {
         "float scale, Tensor(a!) out) -> ()");
   m.def("rep_penalty_(Tensor(a!) logits, Tensor ids, Tensor penalty) -> ()");
   m.def("decode_set_dbg(Tensor dbg) -> ()");
+  m.def("sample_rows(Tensor logits, Tensor inv_t, Tensor top_p, Tensor penalty, Tensor u, Tensor greedy, "
+        "Tensor seen_slot, Tensor(s!) seen, Tensor in_ids, Tensor(o!) out_ids, Tensor(t!) tok, "
+        "Tensor(v!)? out_v=None, Tensor(i!)? out_i=None, Tensor(l!)? out_lse=None) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(lumen, CUDA, m) {
@@ -225,4 +284,5 @@ TORCH_LIBRARY_IMPL(lumen, CUDA, m) {
   m.impl("rep_penalty_", &rep_penalty_);
   m.impl("upload_small", &upload_small);
   m.impl("decode_set_dbg", &decode_set_dbg);
+  m.impl("sample_rows", &sample_rows);
 }

@@ -1,0 +1,35 @@
+// Device vocab sampler (sampler.hip): repetition penalty, temperature, top-64 candidates,
+// nucleus cut and the draw itself in one or two launches that never write the logits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace lumen {
+
+constexpr int SAMPLE_K = 64;   // candidates per row = one wave
+
+struct SampleArgs {
+  const float* logits;      // [B, V] rows of stride ld; read only
+  int64_t ld;
+  int B, V;
+  const float* inv_t;       // [B] 1 / temperature (1 for a greedy row)
+  const double* top_p;      // [B] nucleus mass
+  const float* penalty;     // [B] repetition penalty
+  const double* u;          // [B] the uniform of this token (unused by a greedy row)
+  const int* greedy;        // [B] != 0: take the best candidate
+  const int* seen_slot;     // [B] row of `seen`, or -1: no penalty, nothing marked
+  int* seen;                // [S, words] bitmaps of the tokens already fed, bit t of a row = token t
+  int S, words;             // words = ceil(V / 32)
+  const int64_t* in_ids;    // [B] the step's input tokens (penalised like seen ones, then marked)
+  int64_t* out_ids;         // [B] sampled tokens; may be the same buffer as in_ids
+  int* tok;                 // [B] sampled tokens for the host (-1: no finite logit in the row)
+  float* out_v;             // optional [B, 64] candidate values (transformed logits, descending)
+  int* out_i;               // optional [B, 64] candidate token ids
+  float* out_lse;           // optional [B] log-sum-exp of the transformed row
+};
+
+// floats of workspace sample_rows needs for B rows of V columns (0: single launch)
+int64_t sample_ws_floats(int B, int V);
+hipError_t sample_rows(const SampleArgs& a, float* ws, hipStream_t stream);
+
+}  // namespace lumen

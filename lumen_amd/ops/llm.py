@@ -1,5 +1,5 @@
 """Decoder-LLM ops: RoPE tables, fused RoPE + paged KV write, paged decode attention,
-repetition penalty, candidate sampling.
+repetition penalty, candidate sampling, the device vocab sampler.
 
 GPU tensors run the HIP kernels of csrc/llm.hip; CPU tensors run fp32 references with
 the same semantics (cache layouts in csrc/llm.h: k [NB, Hkv, 64, D], v [NB, Hkv, D, 64]).
@@ -249,3 +249,80 @@ def sample_from_candidates(vals: np.ndarray, idx: np.ndarray, lse: float, temper
     n = max(1, min(n, len(p)))
     q = p[:n] / p[:n].sum()
     return int(idx[int(rng.choice(n, p=q))])
+
+
+SAMPLE_K = 64      # candidates of the device sampler (csrc/sampler.h SAMPLE_K)
+
+
+def seen_words(V: int) -> int:
+    """int32 words of one row of the sampler's seen-token bitmap"""
+    return -(-V // 32)
+
+
+def sample_rows(logits: torch.Tensor, inv_t, top_p, penalty, u, greedy, seen_slot, seen: torch.Tensor, in_ids,
+                out_ids: Optional[torch.Tensor] = None, candidates: bool = True):
+    """Penalise, scale, cut and draw one token per row of fp32 ``logits`` [B, V] without writing them:
+    what :func:`rep_penalty_`, the 1/T multiply, ``row_topk(64)`` and :func:`sample_from_candidates`
+    do in turn on the host path.
+
+    Per row b: ``inv_t`` (1/temperature, 1 for a greedy row), ``top_p``, ``penalty``, the uniform
+    ``u`` (fp64; what ``Generator.choice`` would draw), ``greedy`` (take the best candidate, ``u``
+    unused) and ``seen_slot``: the row of ``seen`` (int32 [S, ceil(V / 32)], bit t = token t was
+    fed before) whose tokens, with ``in_ids[b]``, are penalised; -1: no penalty.  ``in_ids[b]`` is
+    then marked in that row.  ``out_ids`` (int64 [B], may be ``in_ids``) receives the tokens.
+
+    Returns ``(v [B, 64], i [B, 64], lse [B], tok [B] int32, seen)``; ``v`` are the transformed
+    logits of the candidates, descending.  ``candidates=False`` on the GPU: ``v, i, lse`` are None.
+    CPU tensors run an fp32 / fp64 reference of the same operations."""
+    d = logits.device
+    B, V = logits.shape
+    as_t = lambda x, dt: torch.as_tensor(x, dtype=dt, device=d).reshape(B).contiguous()  # noqa: E731
+    inv_t, penalty = as_t(inv_t, torch.float32), as_t(penalty, torch.float32)
+    top_p, u = as_t(top_p, torch.float64), as_t(u, torch.float64)
+    greedy, seen_slot = as_t(greedy, torch.int32), as_t(seen_slot, torch.int32)
+    in_ids = as_t(in_ids, torch.long)
+    if out_ids is None:
+        out_ids = torch.empty(B, dtype=torch.long, device=d)
+    if logits.is_cuda:
+        tok = torch.empty(B, dtype=torch.int32, device=d)
+        v = torch.empty((B, SAMPLE_K), dtype=torch.float32, device=d) if candidates else None
+        i = torch.empty((B, SAMPLE_K), dtype=torch.int32, device=d) if candidates else None
+        lse = torch.empty(B, dtype=torch.float32, device=d) if candidates else None
+        hip_ops().sample_rows(logits, inv_t, top_p, penalty, u, greedy, seen_slot, seen, in_ids, out_ids, tok,
+                              v, i, lse)
+        return v, i, lse, tok, seen
+    if V < SAMPLE_K:
+        raise ValueError(f"sample_rows: V >= {SAMPLE_K}")
+    x = logits.float().clone()
+    feed = in_ids.tolist()
+    shifts = torch.arange(32)
+    for b in range(B):
+        slot = int(seen_slot[b])
+        if slot < 0 or slot >= seen.shape[0] or float(penalty[b]) == 1.0:
+            continue
+        hit = ((seen[slot].long()[:, None] >> shifts) & 1).bool().reshape(-1)[:V]
+        if 0 <= feed[b] < V:
+            hit[feed[b]] = True
+        idx = hit.nonzero().reshape(-1)
+        xv = x[b, idx]
+        x[b, idx] = torch.where(xv > 0, xv / penalty[b], xv * penalty[b])
+    x *= inv_t[:, None]
+    v, i = torch.topk(x, SAMPLE_K, dim=-1, largest=True, sorted=True)
+    lse = torch.logsumexp(x, dim=-1)
+    tok = torch.empty(B, dtype=torch.int32)
+    vn, lsen = v.numpy(), lse.numpy()
+    for b in range(B):
+        j = 0
+        if not int(greedy[b]):
+            tp = float(top_p[b])
+            c = np.cumsum(np.exp(vn[b].astype(np.float64) - np.float64(lsen[b])))
+            n = int(np.searchsorted(c, tp * c[-1] if c[-1] < tp else tp) + 1)
+            n = max(1, min(n, SAMPLE_K))
+            j = min(n - 1, int(np.searchsorted(c[:n] / c[n - 1], float(u[b]), side="right")))
+        tok[b] = i[b, j]
+        slot = int(seen_slot[b])
+        if 0 <= slot < seen.shape[0] and 0 <= feed[b] < V:
+            bit = 1 << (feed[b] & 31)
+            seen[slot, feed[b] >> 5] |= bit - (1 << 32) if bit >> 31 else bit
+    out_ids.copy_(tok.long())
+    return v, i.to(torch.int32), lse, tok, seen

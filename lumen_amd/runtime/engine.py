@@ -83,6 +83,10 @@ class GenRequest:
     done: int = 0                           # prompt tokens prefilled so far
     cached_tokens: int = 0                  # leading prompt tokens taken from the prefix index (not computed)
     prefix_keys: Any = None                 # uint64 [n, 2] content keys of the prompt's full blocks
+    seen_slot: Optional[int] = None         # in-graph sampler: row of the seen-token bitmap (penalised requests)
+    seen_n: int = 0                         # ... tokens[:seen_n] are marked in it by the steps launched so far
+    us: dict = field(default_factory=dict)  # ... token index -> its uniform, drawn once in token order
+    u_next: int = -1                        # ... first token index whose uniform is not drawn yet
 
     def stream(self, timeout: Optional[float] = None) -> Iterator[tuple]:
         """yields ("token", id) ... then ("done", reason) | raises the engine error."""
@@ -387,6 +391,15 @@ class DecodeGraphs:
     result buffer is the IPC all-reduce error flag, copied after the step's last all-reduce:
     the leader sees it in the same D2H as the tokens, before emitting them.  Staging and result
     buffers are double-buffered and fenced by the event of the launch that last used them.
+
+    ``mode="sample"`` graphs (single GPU, captured on first need; the greedy graphs, their step
+    buffer and their result buffer are untouched by them) end in the device sampler
+    (``sample_rows``, csrc/sampler.hip) instead of the top-8 + arg-max: repetition penalty over a
+    per-request bitmap of the tokens fed so far (``seen``, one row = "slot" per penalised
+    request), temperature, top-64 candidates, nucleus cut and the draw with a uniform the host
+    supplies, so sampled and penalised requests replay and look ahead like greedy ones.  Their step
+    buffer also carries per-row 1/T, top_p, penalty, greedy flag, bitmap slot and uniform; their
+    result buffer is the tokens plus the error word.  Padded rows are greedy with slot -1.
     """
 
     BUCKETS = (1, 2, 4, 8, 16, 32, 64, 128)
@@ -403,6 +416,10 @@ class DecodeGraphs:
         self.pool = None
         self.in_graph_sampler = not llm.tp.enabled or os.environ.get("LUMEN_TP_INGRAPH_SAMPLER", "1") == "1"
         self._stream = None     # the capture stream, private to this instance (see _capture_stream)
+        # sample mode: seen-token bitmaps [max_batch, ceil(V / 32)] int32 (19 KB per row at V = 151,936)
+        self.max_batch = max(max_batch, 1)
+        self.seen: Optional[torch.Tensor] = None
+        self._free_slots = list(range(self.max_batch - 1, -1, -1))
 
     def _bucket(self, B: int) -> int:
         for b in self.buckets:
@@ -427,6 +444,45 @@ class DecodeGraphs:
         return {"slots": (0, Bp), "pos": (o_pos, Bp), "ctx": (o_ctx, Bp), "bt": (o_bt, Bp * W),
                 "bytes": -(-(o_bt + 4 * Bp * W) // 16) * 16}
 
+    @staticmethod
+    def _layout_sample(Bp: int, W: int) -> dict:
+        """the greedy layout followed by the sampler's rows: (u f64, top_p f64, inv_t f32, penalty
+        f32, greedy i32, seen_slot i32); the f64 rows start 16-byte aligned"""
+        lay = dict(DecodeGraphs._layout(Bp, W))
+        o = lay["bytes"]
+        for k, sz in (("u", 8), ("top_p", 8), ("inv_t", 4), ("penalty", 4), ("greedy", 4), ("seen_slot", 4)):
+            lay[k] = (o, Bp)
+            o += sz * Bp
+        lay["bytes"] = -(-o // 16) * 16
+        return lay
+
+    _SAMPLE_ROWS = {"u": torch.float64, "top_p": torch.float64, "inv_t": torch.float32, "penalty": torch.float32,
+                    "greedy": torch.int32, "seen_slot": torch.int32}
+    _SAMPLE_PAD = {"u": 0.0, "top_p": 1.0, "inv_t": 1.0, "penalty": 1.0, "greedy": 1, "seen_slot": -1}
+
+    def _seen(self) -> torch.Tensor:
+        if self.seen is None:
+            self.seen = torch.zeros((self.max_batch, lops.seen_words(self.llm.Vl)), dtype=torch.int32,
+                                    device=self.llm.embed.device)
+        return self.seen
+
+    def take_slot(self) -> Optional[int]:
+        """a free row of the seen bitmap (None: all taken); fill it with :meth:`write_slot`"""
+        return self._free_slots.pop() if self._free_slots else None
+
+    def free_slot(self, slot: int) -> None:
+        self._free_slots.append(slot)
+
+    def write_slot(self, slot: int, tokens: Sequence[int]) -> None:
+        """Set row ``slot`` of the bitmap to exactly ``tokens`` (none: zero it), on the current
+        stream -- the one the graphs replay on, so it lands after every step launched before."""
+        seen = self._seen()
+        row = np.zeros(seen.shape[1], np.uint32)
+        t = np.asarray([x for x in tokens if 0 <= x < self.llm.Vl], np.int64)
+        if len(t):
+            np.bitwise_or.at(row, t >> 5, np.uint32(1) << (t & 31).astype(np.uint32))
+        seen[slot].copy_(torch.from_numpy(row.view(np.int32)))
+
     def _capture_stream(self, d: torch.device) -> torch.cuda.Stream:
         """One stream per engine that nothing else ever uses.  The split-K tickets and
         workspaces the kernels key by stream are baked into the graphs captured on it; a
@@ -436,9 +492,10 @@ class DecodeGraphs:
             self._stream = ops.private_stream(d)
         return self._stream
 
-    def _capture(self, Bp: int, W: int) -> dict:
+    def _capture(self, Bp: int, W: int, mode: str = "greedy") -> dict:
         d = self.llm.embed.device
-        lay = self._layout(Bp, W)
+        sample = mode == "sample"
+        lay = self._layout_sample(Bp, W) if sample else self._layout(Bp, W)
         dbuf = torch.zeros(lay["bytes"], dtype=torch.uint8, device=d)
 
         def views(buf):
@@ -449,16 +506,26 @@ class DecodeGraphs:
                 v[k] = buf[o:o + 4 * n].view(torch.int32)
             o, n = lay["bt"]
             v["bt"] = buf[o:o + 4 * n].view(torch.int32).view(Bp, W)
+            if sample:
+                for k, dt in self._SAMPLE_ROWS.items():
+                    o, n = lay[k]
+                    v[k] = buf[o:o + dt.itemsize * n].view(dt)
             return v
 
         st = views(dbuf)
         st["slots"].fill_(-1)
         st["ctx"].fill_(1)
+        if sample:
+            for k, pad in self._SAMPLE_PAD.items():
+                st[k].fill_(pad)
         if Bp not in self.ids:
             self.ids[Bp] = torch.zeros(Bp, dtype=torch.long, device=d)
         ids = self.ids[Bp]
         k = self.K_GREEDY
         res = torch.zeros(2 * Bp * k + Bp + 1, dtype=torch.float32, device=d) if self.in_graph_sampler else None
+        if sample:
+            res = torch.zeros(Bp + 1, dtype=torch.int32, device=d)      # tokens + the error word
+            seen = self._seen()
         tp = self.llm.tp
         KP = 2 * k + 4                      # per-row candidate record: k values, k ids, lse, pad to 16 B
         gat = torch.zeros((tp.world, Bp, KP), dtype=torch.float32, device=d) if res is not None and tp.enabled \
@@ -468,7 +535,11 @@ class DecodeGraphs:
 
         def run():
             logits = self.llm.decode(ids, st["pos"], st["slots"], self.kv, st["bt"], st["ctx"], workspace=ws)
-            if res is not None:
+            if sample:
+                # reads ids (the step's input tokens: penalised and marked) and writes the drawn ones back
+                ops.hip_ops().sample_rows(logits, st["inv_t"], st["top_p"], st["penalty"], st["u"], st["greedy"],
+                                          st["seen_slot"], seen, ids, ids, res[:Bp], None, None, None)
+            elif res is not None:
                 v = res[:Bp * k].view(Bp, k)
                 i = res[Bp * k:2 * Bp * k].view(torch.int32).view(Bp, k)
                 lse = res[2 * Bp * k:2 * Bp * k + Bp]
@@ -517,21 +588,23 @@ class DecodeGraphs:
         ent = {"g": g, "st": st, "dbuf": dbuf, "out": out, "ws": ws, "res": res, "lay": lay, "Bp": Bp, "W": W,
                "h_step": [pin(dbuf) for _ in range(2)], "h_ids": [pin(ids) for _ in range(2)],
                "h_res": [pin(res) for _ in range(2)] if res is not None else None,
-               "ev": [None, None], "par": 0}
+               "ev": [None, None], "par": 0, "mode": mode}
         ent["h_views"] = [views(h) for h in ent["h_step"]]
-        self.graphs[(Bp, W)] = ent
+        self.graphs[(Bp, W, mode)] = ent
         return ent
 
-    def _entry(self, B: int, width: int) -> dict:
-        key = (self._bucket(B), self._width(width))
+    def _entry(self, B: int, width: int, mode: str = "greedy") -> dict:
+        key = (self._bucket(B), self._width(width), mode)
         return self.graphs[key] if key in self.graphs else self._capture(*key)
 
-    def launch(self, ids, pos, slots, bt, ctx, fetch: bool = True) -> dict:
+    def launch(self, ids, pos, slots, bt, ctx, fetch: bool = True, sample: Optional[dict] = None) -> dict:
         """Stage + replay one step (host arrays; ``ids=None``: the token ids the previous
         replay of this batch bucket wrote on the device).  Returns a handle for
-        :meth:`tokens` / :meth:`logits`.  ``fetch=False`` (TP followers): no result copy."""
+        :meth:`tokens` / :meth:`logits`.  ``fetch=False`` (TP followers): no result copy.
+        ``sample``: per-row arrays of the device sampler (keys of ``_SAMPLE_ROWS``) -- the step
+        runs the ``sample`` graph and :meth:`sampled` reads its tokens."""
         B = len(pos)
-        e = self._entry(B, bt.shape[1])
+        e = self._entry(B, bt.shape[1], "greedy" if sample is None else "sample")
         Bp, W = e["Bp"], e["W"]
         par = e["par"]
         e["par"] ^= 1
@@ -548,6 +621,11 @@ class DecodeGraphs:
         cx[:B] = ctx
         tb[:] = 0
         tb[:B, :w] = bt[:, :w]
+        if sample is not None:
+            for k, pad in self._SAMPLE_PAD.items():
+                a = hv[k].numpy()
+                a[:] = pad
+                a[:B] = sample[k]
         e["dbuf"].copy_(e["h_step"][par], non_blocking=True)
         if ids is not None:
             hi = e["h_ids"][par].numpy()
@@ -574,6 +652,14 @@ class DecodeGraphs:
         i = r[Bp * k:2 * Bp * k].view(torch.int32).view(Bp, k)[:B].numpy()
         return v, i, r[2 * Bp * k:2 * Bp * k + B].numpy()
 
+    def sampled(self, h: dict) -> np.ndarray:
+        """tokens [B] int32 of a launched ``sample`` step (waits for it); sets ``h["err"]``"""
+        e, B = h["e"], h["B"]
+        h["ev"].synchronize()
+        r = e["h_res"][h["par"]].numpy()
+        h["err"] = int(r[e["Bp"]])
+        return r[:B]
+
     def run(self, ids, pos, slots, bt, ctx) -> torch.Tensor:
         """Replay one step and return its logits [B, V/tp] (device, valid until the next replay)."""
         h = self.launch(ids, pos, slots, bt, ctx)
@@ -584,9 +670,12 @@ class LLMEngine:
     def __init__(self, llm, kv: PagedKVCache, prefill_builder: Callable[[Any], torch.Tensor], max_batch: int = 64,
                  max_prefill_per_step: int = 4, tp_sync: Optional[TPSync] = None, name: str = "vlm",
                  use_graphs: Optional[bool] = None, prefill_chunk: Optional[int] = None,
-                 follower_args: Optional[Callable[[Any], Any]] = None):
+                 follower_args: Optional[Callable[[Any], Any]] = None, ingraph_sampling: Optional[bool] = None):
         """``follower_args``: what the TP followers receive instead of the prefill arguments
-        (the VLM strips the image: only rank 0 decodes it and runs the vision tower)."""
+        (the VLM strips the image: only rank 0 decodes it and runs the vision tower).
+        ``ingraph_sampling``: sampled / penalised requests decode through the graphs' device
+        sampler with look-ahead (single GPU; None: env ``LUMEN_INGRAPH_SAMPLING``, default on).
+        Off: they take the synchronous host path, as they always do under TP and without graphs."""
         self.llm = llm
         self.kv = kv
         self.build = prefill_builder
@@ -615,6 +704,9 @@ class LLMEngine:
         if use_graphs and self.device.type == "cuda":
             self.graphs = DecodeGraphs(llm, kv, max_batch, -(-llm.cfg.max_position // 64))
         self.follower_args = follower_args
+        if ingraph_sampling is None:
+            ingraph_sampling = os.environ.get("LUMEN_INGRAPH_SAMPLING", "1") != "0"
+        self.ingraph_sampling = bool(ingraph_sampling) and tp_sync is None and not llm.tp.enabled
         self._thread = threading.Thread(target=self._loop, name=f"lumen-{name}-engine", daemon=True)
         self._thread.start()
 
@@ -703,13 +795,34 @@ class LLMEngine:
             return True
         return False
 
+    @staticmethod
+    def _penalised(r: GenRequest) -> bool:
+        return abs(float(r.params.repetition_penalty) - 1.0) > 1e-6
+
+    def _join(self, r: GenRequest) -> None:
+        """``r`` enters the running batch; a penalised request takes a zeroed row of the device
+        sampler's seen bitmap (none free, or no graphs: its batches sample on the host)"""
+        if self.ingraph_sampling and self.graphs is not None and self._penalised(r):
+            r.seen_slot = self.graphs.take_slot()
+            if r.seen_slot is not None:
+                self.graphs.write_slot(r.seen_slot, r.tokens[:-1])
+                r.seen_n = len(r.tokens) - 1
+        self._running.append(r)
+
+    def _drop_slot(self, r: GenRequest) -> None:
+        if r.seen_slot is not None and self.graphs is not None:
+            self.graphs.free_slot(r.seen_slot)
+        r.seen_slot = None
+
     def _finish(self, r: GenRequest) -> None:
+        self._drop_slot(r)
         self.kv.blocks.release(r.rid)
         r.t_done = time.perf_counter()
         r.out.put(("done", r.finish_reason or "stop"))
 
     def _fail(self, reqs, e: BaseException) -> None:
         for r in reqs:
+            self._drop_slot(r)
             try:
                 self.kv.blocks.release(r.rid)
             except Exception:
@@ -787,7 +900,7 @@ class LLMEngine:
         if self._emit(r, tok):
             self._finish(r)
         else:
-            self._running.append(r)
+            self._join(r)
         return e - s
 
     def _prefill_round(self) -> None:
@@ -816,7 +929,52 @@ class LLMEngine:
                 and spec["inv"] is None and spec["pen"] is None and spec["k"] <= g.K_GREEDY
                 and len(reqs) <= g.buckets[-1])
 
-    def _graph_ready(self, reqs) -> bool:
+    def _sample_graph_ok(self, reqs, spec) -> bool:
+        """the in-graph device sampler serves this step: single GPU, graphs and look-ahead on, at
+        most 64 candidates per row, and every penalised request holds a bitmap slot"""
+        g = self.graphs
+        return (self.ingraph_sampling and g is not None and _LOOKAHEAD and spec["k"] <= Sampler.K_SAMPLE
+                and len(reqs) <= g.buckets[-1] and self.llm.Vl >= lops.SAMPLE_K
+                and all(r.seen_slot is not None for r in reqs if self._penalised(r)))
+
+    def _uniform(self, r: GenRequest, n: int) -> float:
+        """the uniform of token ``n`` of ``r``: ``r.rng.random()``, which is what the host path's
+        ``Generator.choice`` draws for it -- once, in token order, kept for a step that is launched
+        again after a discarded look-ahead"""
+        if r.params.temperature <= 0:
+            return 0.0
+        if r.u_next < 0:
+            r.u_next = len(r.tokens)          # the tokens so far were sampled on the host
+        while r.u_next <= n:
+            r.us[r.u_next] = float(r.rng.random())
+            r.u_next += 1
+        r.us.pop(n - 2, None)
+        return r.us[n]
+
+    def _sample_inputs(self, reqs, ahead: int, fed: bool) -> dict:
+        """per-row inputs of the device sampler for the step that yields token len(tokens) + ahead;
+        ``fed``: the step gets its input tokens from the host (not a look-ahead)"""
+        g = self.graphs
+        for r in reqs:
+            if r.seen_slot is None:
+                continue
+            n = len(r.tokens)
+            if fed:
+                if r.seen_n not in (n - 1, n):    # steps of this request ran elsewhere: rebuild its row
+                    g.write_slot(r.seen_slot, r.tokens[:-1])
+                r.seen_n = n                      # this step marks tokens[-1]
+            else:
+                r.seen_n = n + 1                  # ... and this one the token the step before it draws
+        ps = [r.params for r in reqs]
+        return {"inv_t": np.array([1.0 / p.temperature if p.temperature > 0 else 1.0 for p in ps], np.float32),
+                "top_p": np.array([p.top_p for p in ps], np.float64),
+                "penalty": np.array([float(p.repetition_penalty) if r.seen_slot is not None else 1.0
+                                     for p, r in zip(ps, reqs)], np.float32),
+                "greedy": np.array([p.temperature <= 0 for p in ps], np.int32),
+                "seen_slot": np.array([-1 if r.seen_slot is None else r.seen_slot for r in reqs], np.int32),
+                "u": np.array([self._uniform(r, len(r.tokens) + ahead) for r in reqs], np.float64)}
+
+    def _graph_ready(self, reqs, mode: str = "greedy") -> bool:
         """the step's graph exists or captures now (a capture failure disables graphs).  Under
         TP the capture runs collectives, so it happens inside the launch, after the followers
         received the step (they capture the same graph at the same point)."""
@@ -826,7 +984,7 @@ class LLMEngine:
         if self.sync is not None:
             return True
         try:
-            self.graphs._entry(len(reqs), w)
+            self.graphs._entry(len(reqs), w, mode)
             return True
         except Exception as e:  # noqa: BLE001 - capture unsupported: eager launches from now on
             log.warning("hipGraph decode disabled: %s", e)
@@ -858,24 +1016,35 @@ class LLMEngine:
         reqs = self._running
         B = len(reqs)
         spec = Sampler.spec(reqs)
-        if self._greedy_graph_ok(reqs, spec) and self._graph_ready(reqs):
+        mode = "greedy" if self._greedy_graph_ok(reqs, spec) else "sample" if self._sample_graph_ok(reqs, spec) \
+            else None
+        if mode is not None and self._graph_ready(reqs, mode):
             # look-ahead decode: the step after this one is launched (token ids taken from this
-            # step's in-graph arg-max) BEFORE this step's tokens are read, so the host work of
+            # step's in-graph arg-max or draw) BEFORE this step's tokens are read, so the host work of
             # reading, streaming and scheduling overlaps the GPU instead of idling it between steps
             rids = [r.rid for r in reqs]
+            smp = mode == "sample"       # the mode follows from the requests, so a pending step has the same
             pend, self._pending = self._pending, None
             if pend is not None and pend[0] == rids:
                 h = pend[1]
             else:
                 ids = np.array([r.tokens[-1] for r in reqs], np.int64)
-                h = self._launch_greedy(ids, self._step_inputs(reqs, 0), spec)
-            nxt = self._launch_greedy(None, self._step_inputs(reqs, 1), spec) if self._can_look_ahead(reqs) else None
-            _v, i, _lse = self.graphs.tokens(h)
+                h = self._launch_greedy(ids, self._step_inputs(reqs, 0), spec,
+                                        self._sample_inputs(reqs, 0, True) if smp else None)
+            nxt = None
+            if self._can_look_ahead(reqs):
+                nxt = self._launch_greedy(None, self._step_inputs(reqs, 1), spec,
+                                          self._sample_inputs(reqs, 1, False) if smp else None)
+            if smp:
+                toks = [int(t) for t in self.graphs.sampled(h)]
+                self.stats["ingraph_sample_steps"] = self.stats.get("ingraph_sample_steps", 0) + 1
+            else:
+                _v, i, _lse = self.graphs.tokens(h)
+                toks = [int(i[b, 0]) for b in range(B)]
             if h.get("err"):
                 # an IPC all-reduce of this step gave up on a peer: its tokens are garbage
                 self._pending = None
                 raise TPGroupUnavailable("tensor-parallel peer not responding (IPC all-reduce timed out)")
-            toks = [int(i[b, 0]) for b in range(B)]
             self.stats["decode_steps"] += 1
             still = []
             for r, t in zip(reqs, toks):
@@ -913,13 +1082,14 @@ class LLMEngine:
                 still.append(r)
         self._running = still
 
-    def _launch_greedy(self, ids, inputs, spec) -> dict:
+    def _launch_greedy(self, ids, inputs, spec, sample: Optional[dict] = None) -> dict:
         """One in-graph-sampled step (``ids`` None: look-ahead, ids from the device); under TP the
-        followers get the descriptor first and replay the same graph."""
+        followers get the descriptor first and replay the same graph.  ``sample``: the device
+        sampler's per-row inputs (single GPU) instead of the greedy arg-max."""
         if self.sync is not None:
             self.sync.send_decode(ids, *inputs, spec, graph=True, ingraph=True)
         try:
-            return self.graphs.launch(ids, *inputs)
+            return self.graphs.launch(ids, *inputs, sample=sample)
         except Exception:
             if self.sync is not None:
                 raise            # TP ranks must not diverge

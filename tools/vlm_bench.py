@@ -53,6 +53,10 @@ def main():
                          "previous stream ends)")
     ap.add_argument("--image-kind", choices=["noise", "photo"], default="noise",
                     help="synthetic JPEG content: uniform noise (worst-case host decode) or photo-like")
+    ap.add_argument("--temperature", type=float, default=0.0, help="sampling temperature (0: greedy)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="nucleus mass of sampled requests")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--seed", type=int, default=None, help="sampling seed (stream i of the batched phase: seed + i)")
     args = ap.parse_args()
     load_hip(required=True)
     dev = torch.device("cuda")
@@ -112,11 +116,15 @@ def main():
     text = [int(t) for t in rng.integers(1000, min(V, 30000), args.prompt_tokens)]
     ids = text[:8] + [cfg.image_token_id] + text[8:]
     full, _ = m.expand_image_tokens(ids, 1)
-    eos_none = SamplingParams(max_new_tokens=args.max_new, stop_token_ids=())
+
+    def params(max_new, stream=0):
+        return SamplingParams(max_new_tokens=max_new, temperature=args.temperature, top_p=args.top_p,
+                              repetition_penalty=args.repetition_penalty,
+                              seed=None if args.seed is None else args.seed + stream)
 
     def one(max_new):
         t_arrive = time.perf_counter()
-        r = eng.submit((ids, prepare(ids, decode(jpeg))), len(full), SamplingParams(max_new_tokens=max_new))
+        r = eng.submit((ids, prepare(ids, decode(jpeg))), len(full), params(max_new))
         r.t_arrive = t_arrive
         times = []
         for kind, _ in r.stream(timeout=600):
@@ -152,8 +160,8 @@ def main():
         return
     t1 = time.perf_counter()
     with ThreadPoolExecutor(max_workers=max(args.batch, 1)) as ex:
-        rs = list(ex.map(lambda _: eng.submit((ids, prepare(ids, decode(jpeg))), len(full),
-                                              SamplingParams(max_new_tokens=args.batch_max_new)), range(args.batch)))
+        rs = list(ex.map(lambda i: eng.submit((ids, prepare(ids, decode(jpeg))), len(full),
+                                              params(args.batch_max_new, i)), range(args.batch)))
     # steady-state batched decode: per-token arrival times of every stream; the window starts
     # when the LAST request has its first token (all B in the running batch) and ends when the
     # first request finishes (the batch starts shrinking)
@@ -172,6 +180,10 @@ def main():
     in_win = sum(sum(1 for t in st if w0 < t <= w1) for st in stamps)
     batch_decode = in_win / (w1 - w0) if w1 > w0 else None
     eng.close()
+    sampling = {"temperature": args.temperature, "top_p": args.top_p, "repetition_penalty": args.repetition_penalty,
+                "seed": args.seed, "ingraph": eng.ingraph_sampling,
+                "ingraph_sample_steps": eng.stats.get("ingraph_sample_steps", 0),
+                "lookahead_steps": eng.stats.get("lookahead_steps", 0), "decode_steps": eng.stats["decode_steps"]}
     out = {"metric": "VLM p50 TTFT", "value": float(np.percentile(ttft, 50)), "unit": "ms",
            "higher_is_better": False, "p90_ttft_ms": float(np.percentile(ttft, 90)),
            "p99_ttft_ms": float(np.percentile(ttft, 99)),
@@ -179,7 +191,7 @@ def main():
            "ttft_breakdown_ms": {"queue": float(np.median(queue_ms)), "jpeg_decode": float(np.median(dec_ms[:args.n])),
                                  "admit_to_first_token": float(np.median(admit_first_ms))},
            "decode_tok_s_single": float(np.median(tps)) if tps else None,
-           "batch": args.batch, "batch_tok_s": ntok / batch_s,
+           "sampling": sampling, "batch": args.batch, "batch_tok_s": ntok / batch_s,
            "batch_decode_tok_s": batch_decode, "batch_note": "batch_tok_s = all tokens / wall time incl. the "
            "B prefills; batch_decode_tok_s = steady-state decode while all B streams run",
            "prompt_tokens": len(full),
