@@ -84,6 +84,33 @@ struct PrefillArgs {
 };
 hipError_t paged_prefill(const PrefillArgs& a, int D, hipStream_t stream);
 
+// Verify attention (speculative decoding): up to T new rows for each of B sequences over the
+// paged cache in one launch.  Row i of sequence b (q / o row b * T + i) sits at position
+// ctx_len[b] - n_rows[b] + i and attends cache tokens 0 .. that position; rows i >= n_rows[b] are
+// padding and come out 0.  The rows' own k / v are already in the cache (rope_kv runs first).
+// Block table, ctx_len and n_rows are read on the device, so a captured launch serves any step.
+// T * (H / Hkv) <= 64.
+struct VerifyArgs {
+  const uint16_t* q;      // [B * T, q_ld] rotated packed QKV rows; head h at h * D
+  int64_t q_ld;
+  const uint16_t* k_cache;
+  const uint16_t* v_cache;
+  const int* block_table; // [B, bt_stride], bt_width entries per row (clamped into the pool)
+  int bt_stride, bt_width;
+  const int* ctx_len;     // [B] tokens in the cache including this step's n_rows[b] rows
+  const int* n_rows;      // [B] live rows, 1 .. T
+  uint16_t* o;            // [B * T, o_ld] rows; head h at h * D
+  int64_t o_ld;
+  float* part_o;          // [B * T, H, nsplit, D]   (nsplit > 1)
+  float* part_ml;         // [B * T, H, nsplit, 2]
+  uint32_t* split_cnt;    // [B, Hkv] zeroed tickets of the in-launch split combine (nsplit > 1)
+  int T, H, Hkv, nsplit, blocks_per_split;   // split policy as DecodeArgs
+  int num_blocks;         // pool size
+  float scale_log2;
+  int kv_fp8;
+};
+hipError_t paged_verify(const VerifyArgs& a, int B, int D, hipStream_t stream);
+
 hipError_t rep_penalty(float* logits, int64_t ld, const int* ids, int maxn, const float* penalty, int B, int V,
                        hipStream_t stream);
 

@@ -13,7 +13,10 @@
 //  * paged_prefill: attention of a chunk of new query rows over the paged cache (chunked
 //    prefill, prefix reuse) with (query row, head) pairs as the MFMA columns and a causal
 //    mask per column.
-//    Both paged kernels are bookkeeping around ONE block step, paged_attn.h: the K / V
+//  * paged_verify: up to T new query rows for each of B sequences in one launch (speculative
+//    decoding): prefill's column mapping on decode's (split, kv-head, sequence) grid and
+//    in-launch split combine, every per-step quantity read from device memory.
+//    All three paged kernels are bookkeeping around ONE block step, paged_attn.h: the K / V
 //    fragment loads straight from HBM (S^T = K Q^T reads K rows in a permuted token order
 //    chosen so that each lane's 8 P values are 8 consecutive tokens, which the transposed
 //    V cache serves with one 16-byte load per MFMA of O^T = V^T P^T), the online-softmax /
@@ -431,11 +434,7 @@ __global__ void __launch_bounds__(64 * PA_NW) paged_decode_kernel(DecodeArgs a, 
       a.o[(int64_t)b * a.o_sb + (int64_t)h * D + d] = f2bf(L > 0.f ? O / L : 0.f);
     } else {
       const int64_t pi = ((int64_t)b * a.H + h) * a.nsplit + split;
-      __hip_atomic_store(a.part_o + pi * D + d, O, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (d == 0) {
-        __hip_atomic_store(a.part_ml + pi * 2, M, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(a.part_ml + pi * 2 + 1, L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      publish_split<D>(a.part_o, a.part_ml, pi, d, M, L, O);
     }
   }
   if (ns == 1) {
@@ -447,50 +446,15 @@ __global__ void __launch_bounds__(64 * PA_NW) paged_decode_kernel(DecodeArgs a, 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (dbg && tid == 0) dbg[5] = (int64_t)__builtin_amdgcn_s_memrealtime();   // partials published
-  if (tid == 0) {
-    uint32_t* c = a.split_cnt + (int64_t)b * a.Hkv + hk;
-    const uint32_t prev = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = prev == (uint32_t)ns - 1;
-    if (last) __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sm_last = last ? 1 : 0;
-  }
+  if (tid == 0) sm_last = split_ticket(a.split_cnt + (int64_t)b * a.Hkv + hk, ns) ? 1 : 0;
   __syncthreads();
   if (dbg && tid == 0) dbg[6] = (int64_t)__builtin_amdgcn_s_memrealtime();   // ticket back
   if (!sm_last) return;
-  // one round trip per 8 splits: every (m, l) and o partial of a chunk is loaded before any is used
-  // (the chunk's max rescales the running sums, online-softmax style); split order: deterministic
   for (int idx = tid; idx < G * D; idx += 64 * NW) {
     const int q = idx / D, d = idx - q * D;
     const int h = hk * G + q;
     const int64_t pi0 = ((int64_t)b * a.H + h) * a.nsplit;
-    float M = -INFINITY, L = 0.f, O = 0.f;
-    for (int s0 = 0; s0 < ns; s0 += 8) {
-      float pm[8], pl[8], pv[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int64_t pi = pi0 + min(s0 + j, ns - 1);
-        pm[j] = __hip_atomic_load(a.part_ml + pi * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        pl[j] = __hip_atomic_load(a.part_ml + pi * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        pv[j] = __hip_atomic_load(a.part_o + pi * D + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      float mc = M;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) mc = s0 + j < ns ? fmaxf(mc, pm[j]) : mc;
-      if (mc == -INFINITY) continue;
-      const float r = __builtin_amdgcn_exp2f(M - mc);   // M = -inf: 0 (L, O still 0)
-      L *= r;
-      O *= r;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if (s0 + j < ns) {
-          const float e = __builtin_amdgcn_exp2f(pm[j] - mc);
-          L += pl[j] * e;
-          O += pv[j] * e;
-        }
-      }
-      M = mc;
-    }
-    a.o[(int64_t)b * a.o_sb + (int64_t)h * D + d] = f2bf(L > 0.f ? O / L : 0.f);
+    a.o[(int64_t)b * a.o_sb + (int64_t)h * D + d] = f2bf(merge_splits<D>(a.part_o, a.part_ml, pi0, ns, d));
   }
   if (dbg && tid == 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -615,6 +579,141 @@ hipError_t paged_prefill(const PrefillArgs& a, int D, hipStream_t stream) {
   dim3 grid((a.T + QT - 1) / QT, a.Hkv), block(64 * PA_NW);
   const bool ok = pa_dispatch(D, a.kv_fp8, [&](auto d, auto f8) {
     hipLaunchKernelGGL((paged_prefill_kernel<decltype(d)::value, decltype(f8)::value>), grid, block, 0, stream, a);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// ------------------------------------------------------------------------------ paged verify attention
+// Up to T new query rows for each of B sequences in one launch (speculative decoding: the last
+// accepted token plus its draft tokens).  Prefill's column mapping on decode's grid: one workgroup
+// of 4 waves per (split, kv head, sequence) with decode's split policy (blocks per split derived
+// from each sequence's ctx_len on the device) and its in-launch combine; MFMA column c <-> row
+// c / G, head hk * G + c % G over NCT = 1, 2 or 4 column tiles (T * G <= 64), so a block's K / V
+// fragments are loaded once per workgroup and reused by every row.  Row i of sequence b sits at
+// position ctx_len[b] - n_rows[b] + i and sees tokens 0 .. that position; rows >= n_rows[b] see
+// nothing and come out 0.  Everything that changes from step to step (block table, ctx_len,
+// n_rows) is read from device memory: one captured graph replays for any step.  The rows' own
+// k / v are in the cache already (rope_kv runs first).
+template <int D, bool F8KV, int NCT>
+__global__ void __launch_bounds__(64 * PA_NW) paged_verify_kernel(VerifyArgs a) {
+  constexpr int NW = PA_NW;
+  constexpr int KS = D / 32;   // k-steps of S^T over the head dim
+  constexpr int NB = D / 16;   // 16-wide d blocks of O^T
+  __shared__ WaveMerge<D> sm;
+  __shared__ int sm_last;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int col = lane & 15, g = lane >> 4;
+  const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+  const int G = a.H / a.Hkv;
+  const int ctx = min(max(a.ctx_len[b], 0), a.bt_width * KV_BLOCK);   // never past the table row
+  const int n = min(max(a.n_rows[b], 0), a.T);
+  const int nblk = (ctx + KV_BLOCK - 1) / KV_BLOCK;
+  const int bps = max(a.blocks_per_split, (nblk + (int)gridDim.x - 1) / (int)gridDim.x);
+  const int blk0 = split * bps;
+  const int blk1 = min(blk0 + bps, nblk);
+  const int ns = max(1, (nblk + bps - 1) / bps);   // splits holding blocks
+  if (split >= ns) return;
+  const int* bt = a.block_table + (int64_t)b * a.bt_stride;
+  int phys = blk0 + wid < blk1 ? bt[blk0 + wid] : 0;   // first load of the chain
+
+  // Q^T fragments (B operand) of the column tiles; lim = tokens the column may see (0: padding)
+  bf16x8_t qf[NCT][KS];
+  int lim[NCT];
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+    const int c = ct * 16 + col;
+    const int rl = c / G, hg = c - rl * G;
+    const bool ok = rl < n;
+    lim[ct] = ok ? ctx - n + rl + 1 : 0;
+    const uint16_t* qp = a.q + ((int64_t)b * a.T + (ok ? rl : 0)) * a.q_ld + (int64_t)(hk * G + hg) * D;
+#pragma unroll
+    for (int t = 0; t < KS; ++t) {
+      u32x4_t w = *(const u32x4_t*)(qp + t * 32 + g * 8);
+      if (!ok) w = (u32x4_t){0u, 0u, 0u, 0u};
+      qf[ct][t] = __builtin_bit_cast(bf16x8_t, w);
+    }
+  }
+
+  f32x4_t o[NCT][NB];
+  float mrow[NCT], lrow[NCT];
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+    mrow[ct] = -INFINITY;
+    lrow[ct] = 0.f;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) o[ct][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  }
+
+  for (int bi = blk0 + wid; bi < blk1; bi += NW) {
+    if (bi != blk0 + wid) phys = bt[bi];
+    phys = min(max(phys, 0), a.num_blocks - 1);   // a bad table entry must not leave the pool
+    const int tok0 = bi * KV_BLOCK;
+    bf16x8_t kf[4][KS];
+    bf16x8_t vf[2][NB];
+    load_kv_block<D, F8KV>(a.k_cache, a.v_cache, ((int64_t)phys * a.Hkv + hk) * KV_BLOCK * D, col, g, kf, vf);
+    zero_v_tail(vf, min(KV_BLOCK, ctx - tok0), g);
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct) {
+      if (ct * 16 >= n * G) continue;   // a tile of padding columns only (workgroup-uniform)
+      f32x4_t sc[4];
+      qk_scores(kf, qf[ct], sc);
+      softmax_step(sc, lim[ct] - tok0, a.scale_log2, g, mrow[ct], lrow[ct], o[ct]);
+      pv_step(sc, vf, o[ct]);
+    }
+  }
+
+  // ---- merge the NW wave states through LDS, one column tile at a time
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+    if (ct > 0) __syncthreads();
+    sm.store(wid, col, g, mrow[ct], lrow[ct], o[ct]);
+    __syncthreads();
+    for (int idx = tid; idx < 16 * D; idx += 64 * NW) {
+      const int qc = idx / D, d = idx - qc * D;
+      const int c = ct * 16 + qc;
+      const int rl = c / G, hg = c - rl * G;
+      if (rl >= a.T) continue;
+      float M, L, O;
+      sm.reduce(qc, d, M, L, O);
+      const int64_t row = (int64_t)b * a.T + rl;
+      const int h = hk * G + hg;
+      if (ns == 1) a.o[row * a.o_ld + (int64_t)h * D + d] = f2bf(L > 0.f ? O / L : 0.f);
+      else publish_split<D>(a.part_o, a.part_ml, (row * a.H + h) * a.nsplit + split, d, M, L, O);
+    }
+  }
+  if (ns == 1) return;
+
+  // ---- in-launch combine: the last split of (b, hk) to arrive merges all ns splits
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) sm_last = split_ticket(a.split_cnt + (int64_t)b * a.Hkv + hk, ns) ? 1 : 0;
+  __syncthreads();
+  if (!sm_last) return;
+  for (int idx = tid; idx < a.T * G * D; idx += 64 * NW) {
+    const int c = idx / D, d = idx - c * D;
+    const int rl = c / G, hg = c - rl * G;
+    const int64_t row = (int64_t)b * a.T + rl;
+    const int h = hk * G + hg;
+    a.o[row * a.o_ld + (int64_t)h * D + d] = f2bf(merge_splits<D>(a.part_o, a.part_ml, (row * a.H + h) * a.nsplit, ns, d));
+  }
+}
+
+hipError_t paged_verify(const VerifyArgs& a, int B, int D, hipStream_t stream) {
+  if (B <= 0) return hipSuccess;
+  if (a.T < 1 || a.Hkv <= 0 || a.H % a.Hkv != 0 || a.H / a.Hkv > 16 || a.T * (a.H / a.Hkv) > 64 || a.num_blocks <= 0 ||
+      a.bt_width <= 0 || a.nsplit < 1 || a.nsplit > 32 || a.blocks_per_split < 1 ||
+      (a.nsplit > 1 && (a.split_cnt == nullptr || a.part_o == nullptr || a.part_ml == nullptr)))
+    return hipErrorInvalidValue;
+  const int cols = a.T * (a.H / a.Hkv);
+  dim3 grid(a.nsplit, a.Hkv, B), block(64 * PA_NW);
+  const bool ok = pa_dispatch(D, a.kv_fp8, [&](auto d, auto f8) {
+    constexpr int Dc = decltype(d)::value;
+    constexpr bool F8 = decltype(f8)::value;
+    if (cols <= 16) hipLaunchKernelGGL((paged_verify_kernel<Dc, F8, 1>), grid, block, 0, stream, a);
+    else if (cols <= 32) hipLaunchKernelGGL((paged_verify_kernel<Dc, F8, 2>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((paged_verify_kernel<Dc, F8, 4>), grid, block, 0, stream, a);
   });
   return ok ? hipGetLastError() : hipErrorInvalidValue;
 }

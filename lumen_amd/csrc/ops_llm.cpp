@@ -1,5 +1,5 @@
 // torch.ops.lumen.* registration of the decoder-LLM kernels (llm.hip): fused RoPE +
-// paged KV-cache write, paged flash-decoding attention, paged prefill attention, repetition penalty.
+// paged KV-cache write, paged flash-decoding attention, paged prefill / verify attention, repetition penalty.
 #include <ATen/ATen.h>
 #include <ATen/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -173,6 +173,61 @@ void paged_prefill(const at::Tensor& q, const at::Tensor& k_cache, const at::Ten
   CHECK_HIP3(lumen::paged_prefill(a, (int)D, cur()));
 }
 
+// q [B * T, >= H D] rows of the rotated packed QKV buffer (bf16), sequence-major; block_table int32 [B, W];
+// ctx_len / n_rows int32 [B]; out [B * T, >= H D] rows.  T * (H / Hkv) <= 64.
+void paged_verify(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                  const at::Tensor& block_table, const at::Tensor& ctx_len, const at::Tensor& n_rows, at::Tensor out,
+                  int64_t T, int64_t H, int64_t Hkv, double scale, int64_t nsplit, int64_t blocks_per_split,
+                  const c10::optional<at::Tensor>& part_o, const c10::optional<at::Tensor>& part_ml) {
+  TORCH_CHECK(k_cache.dim() == 4, "k_cache: [NB, Hkv, 64, D]");
+  const int64_t D = k_cache.size(3);
+  const int kv_fp8 = check_cache(k_cache, v_cache, Hkv, D);
+  TORCH_CHECK(D == 32 || D == 64 || D == 128, "paged_verify: head dim 32, 64 or 128");
+  TORCH_CHECK(Hkv > 0 && H % Hkv == 0 && H / Hkv <= 16, "paged_verify: at most 16 query heads per kv head");
+  TORCH_CHECK(T >= 1 && T * (H / Hkv) <= 64, "paged_verify: T * (H / Hkv) must be in 1 .. 64");
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && q.dim() == 2 && q.stride(1) == 1 && q.size(1) >= H * D &&
+              q.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 && q.size(0) % T == 0,
+              "paged_verify: q rows");
+  const int64_t B = q.size(0) / T;
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 && out.dim() == 2 && out.stride(1) == 1 &&
+              out.size(1) >= H * D && out.size(0) == B * T, "paged_verify: out rows");
+  TORCH_CHECK(block_table.is_cuda() && block_table.scalar_type() == at::kInt && block_table.dim() == 2 &&
+              block_table.size(0) == B && block_table.size(1) >= 1 && block_table.stride(1) == 1,
+              "block_table int32 [B, max_blocks]");
+  TORCH_CHECK(ctx_len.is_cuda() && ctx_len.scalar_type() == at::kInt && ctx_len.numel() == B && ctx_len.is_contiguous(),
+              "ctx_len int32 [B]");
+  TORCH_CHECK(n_rows.is_cuda() && n_rows.scalar_type() == at::kInt && n_rows.numel() == B && n_rows.is_contiguous(),
+              "n_rows int32 [B]");
+  TORCH_CHECK(q.device() == k_cache.device() && out.device() == q.device() && v_cache.device() == q.device() &&
+              block_table.device() == q.device() && ctx_len.device() == q.device() && n_rows.device() == q.device(),
+              "paged_verify: tensors on one device");
+  TORCH_CHECK(nsplit >= 1 && nsplit <= 32 && blocks_per_split >= 1, "paged_verify: nsplit / blocks_per_split");
+  if (B == 0) return;
+  lumen::VerifyArgs a{};
+  a.q = bfp(q); a.q_ld = q.stride(0);
+  a.k_cache = reinterpret_cast<const uint16_t*>(k_cache.data_ptr());
+  a.v_cache = reinterpret_cast<const uint16_t*>(v_cache.data_ptr());
+  a.kv_fp8 = kv_fp8;
+  a.block_table = block_table.data_ptr<int>(); a.bt_stride = (int)block_table.stride(0);
+  a.bt_width = (int)block_table.size(1);
+  a.ctx_len = ctx_len.data_ptr<int>(); a.n_rows = n_rows.data_ptr<int>();
+  a.o = bfp(out); a.o_ld = out.stride(0);
+  a.T = (int)T; a.H = (int)H; a.Hkv = (int)Hkv; a.nsplit = (int)nsplit; a.blocks_per_split = (int)blocks_per_split;
+  a.num_blocks = (int)k_cache.size(0);
+  a.scale_log2 = (float)(scale * 1.4426950408889634);
+  if (nsplit > 1) {
+    TORCH_CHECK(part_o.has_value() && part_ml.has_value(), "paged_verify: split workspace required");
+    TORCH_CHECK(part_o->scalar_type() == at::kFloat && part_o->is_contiguous() && part_o->device() == q.device() &&
+                part_o->numel() >= B * T * H * nsplit * D, "part_o");
+    TORCH_CHECK(part_ml->scalar_type() == at::kFloat && part_ml->is_contiguous() && part_ml->device() == q.device() &&
+                part_ml->numel() >= B * T * H * nsplit * 2, "part_ml");
+    a.part_o = part_o->data_ptr<float>(); a.part_ml = part_ml->data_ptr<float>();
+    a.split_cnt = lumen::splitk_counters(q, B * Hkv);
+  }
+  const at::DeviceGuard g(q.device());
+  CHECK_HIP3(lumen::paged_verify(a, (int)B, (int)D, cur()));
+}
+
 // profiling: per-workgroup timestamps of paged_decode into dbg [B, Hkv, nsplit, 8] int64 (empty: off)
 void decode_set_dbg(const at::Tensor& dbg) {
   TORCH_CHECK(dbg.is_cuda() && dbg.scalar_type() == at::kLong && dbg.is_contiguous(), "decode_set_dbg: int64");
@@ -270,6 +325,9 @@ TORCH_LIBRARY_FRAGMENT(lumen, m) {
         "Tensor? pf1=None) -> ()");
   m.def("paged_prefill(Tensor q, Tensor k_cache, Tensor v_cache, Tensor blocks, int start_pos, int H, int Hkv, "
         "float scale, Tensor(a!) out) -> ()");
+  m.def("paged_verify(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_table, Tensor ctx_len, Tensor n_rows, "
+        "Tensor(o!) out, int T, int H, int Hkv, float scale, int nsplit, int blocks_per_split, "
+        "Tensor(p!)? part_o=None, Tensor(m!)? part_ml=None) -> ()");
   m.def("rep_penalty_(Tensor(a!) logits, Tensor ids, Tensor penalty) -> ()");
   m.def("decode_set_dbg(Tensor dbg) -> ()");
   m.def("sample_rows(Tensor logits, Tensor inv_t, Tensor top_p, Tensor penalty, Tensor u, Tensor greedy, "
@@ -281,6 +339,7 @@ TORCH_LIBRARY_IMPL(lumen, CUDA, m) {
   m.impl("rope_kv", &rope_kv);
   m.impl("paged_decode", &paged_decode);
   m.impl("paged_prefill", &paged_prefill);
+  m.impl("paged_verify", &paged_verify);
   m.impl("rep_penalty_", &rep_penalty_);
   m.impl("upload_small", &upload_small);
   m.impl("decode_set_dbg", &decode_set_dbg);

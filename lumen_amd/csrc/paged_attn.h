@@ -1,6 +1,6 @@
-// The block step shared by the two attention kernels over the paged KV pools (llm.hip:
-// paged_decode_kernel, paged_prefill_kernel).  A wave takes one 64-token block of one kv head and
-// 16 query columns at a time:
+// The block step shared by the attention kernels over the paged KV pools (llm.hip:
+// paged_decode_kernel, paged_prefill_kernel, paged_verify_kernel).  A wave takes one 64-token block
+// of one kv head and 16 query columns at a time:
 //
 //   load_kv_block    every K and V fragment of the block, straight from HBM (layouts in llm.h)
 //   zero_v_tail      V lanes past the sequence end -> 0 (any time before pv_step)
@@ -181,6 +181,65 @@ struct WaveMerge {
     }
   }
 };
+
+// ---- in-launch combine of a context split over several workgroups (decode, verify): every split
+// publishes its (m, l, o) partials with write-through stores (publish_split), waits for them
+// (s_waitcnt vmcnt(0) + __syncthreads()), draws a ticket (split_ticket), and the last to arrive
+// merges all of them (merge_splits).  part_o [.., nsplit, D], part_ml [.., nsplit, 2]; pi = index
+// of the (row, head, split) record.
+
+template <int D>
+__device__ __forceinline__ void publish_split(float* part_o, float* part_ml, int64_t pi, int d, float M, float L, float O) {
+  __hip_atomic_store(part_o + pi * D + d, O, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (d == 0) {
+    __hip_atomic_store(part_ml + pi * 2, M, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(part_ml + pi * 2 + 1, L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// one thread per workgroup: true for the last of the ns splits to arrive, which also re-zeroes the
+// counter for the next launch
+__device__ __forceinline__ bool split_ticket(uint32_t* c, int ns) {
+  const uint32_t prev = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const bool last = prev == (uint32_t)ns - 1;
+  if (last) __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return last;
+}
+
+// element d of the normalised output over the ns split records from pi0.  One round trip per 8
+// splits: every (m, l) and o partial of a chunk is loaded before any is used (the chunk's max
+// rescales the running sums, online-softmax style); split order: deterministic
+template <int D>
+__device__ __forceinline__ float merge_splits(const float* part_o, const float* part_ml, int64_t pi0, int ns, int d) {
+  float M = -INFINITY, L = 0.f, O = 0.f;
+  for (int s0 = 0; s0 < ns; s0 += 8) {
+    float pm[8], pl[8], pv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int64_t pi = pi0 + min(s0 + j, ns - 1);
+      pm[j] = __hip_atomic_load(part_ml + pi * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      pl[j] = __hip_atomic_load(part_ml + pi * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      pv[j] = __hip_atomic_load(part_o + pi * D + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    float mc = M;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) mc = s0 + j < ns ? fmaxf(mc, pm[j]) : mc;
+    if (mc == -INFINITY) continue;
+    const float r = __builtin_amdgcn_exp2f(M - mc);   // M = -inf: 0 (L, O still 0)
+    L *= r;
+    O *= r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (s0 + j < ns) {
+        const float e = __builtin_amdgcn_exp2f(pm[j] - mc);
+        L += pl[j] * e;
+        O += pv[j] * e;
+      }
+    }
+    M = mc;
+  }
+  return L > 0.f ? O / L : 0.f;
+}
 
 // Host: f(integral_constant<int, D>, bool_constant<fp8 cache>) for the head dims the paged kernels
 // are built for; false = unsupported head dim, f not called.

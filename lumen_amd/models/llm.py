@@ -664,3 +664,22 @@ class LLM(nn.Module):
         self._layers(x, pos, slots, kv, attn)
         dec = self.norm_folded and x.is_cuda and x.shape[0] <= 32 and not self.tp.enabled
         return self.logits(x, ssq=self._ssq if dec else None)
+
+    @torch.no_grad()
+    def verify(self, ids: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor, kv, block_table: torch.Tensor,
+               ctx_len: torch.Tensor, n_rows: torch.Tensor, T: int, workspace: Optional[dict] = None) -> torch.Tensor:
+        """B sequences, up to T new tokens each (speculative decoding: the last accepted token
+        and its drafts) -> logits [B*T, V/tp] fp32, row b*T + i for token i of sequence b.
+        ids / pos / slots [B*T] (padding rows: slot -1); ``ctx_len`` [B] counts the cache tokens
+        including this step's ``n_rows[b]`` live rows.  :meth:`decode` with
+        :func:`lops.paged_verify` as the attention; RoPE and the cache write stay in rope_kv."""
+        x = self.embed_tokens(ids)
+        self._maybe_fold(x)
+
+        def attn(qkv, l, kc, vc):
+            return lops.paged_verify(qkv, kc, vc, block_table, ctx_len, n_rows, T, l.H, l.Hkv, workspace=workspace)
+
+        attn.fuses_rope = False
+        self._layers(x, pos, slots, kv, attn)
+        dec = self.norm_folded and x.is_cuda and x.shape[0] <= 32 and not self.tp.enabled
+        return self.logits(x, ssq=self._ssq if dec else None)

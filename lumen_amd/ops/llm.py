@@ -1,5 +1,5 @@
-"""Decoder-LLM ops: RoPE tables, fused RoPE + paged KV write, paged decode attention,
-repetition penalty, candidate sampling, the device vocab sampler.
+"""Decoder-LLM ops: RoPE tables, fused RoPE + paged KV write, paged decode / prefill / verify
+attention, repetition penalty, candidate sampling, the device vocab sampler.
 
 GPU tensors run the HIP kernels of csrc/llm.hip; CPU tensors run fp32 references with
 the same semantics (cache layouts in csrc/llm.h: k [NB, Hkv, 64, D], v [NB, Hkv, D, 64]).
@@ -210,6 +210,74 @@ def paged_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     p = torch.softmax(s.masked_fill(hidden, float("-inf")), -1)
     o = torch.einsum("hgts,hsd->thgd", p, v)
     out[:, :H * D] = o.reshape(T, H * D).to(out.dtype)
+    return out
+
+
+PAGED_VERIFY_MAX_COLS = 64     # MFMA columns (query row, head in group) of one paged-verify workgroup
+
+
+def paged_verify(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
+                 ctx_len: torch.Tensor, n_rows: torch.Tensor, T: int, H: int, Hkv: int,
+                 scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                 workspace: Optional[dict] = None, splits: Optional[tuple] = None) -> torch.Tensor:
+    """Attention of up to T new rows for each of B sequences over the paged cache in one launch
+    (speculative decoding): q [B*T, >= H*D], sequence-major rows of the rotated packed QKV buffer
+    (may be a view), ``block_table`` int32 [B, W], ``ctx_len`` int32 [B] the tokens in the cache
+    *including* this step's rows, ``n_rows`` int32 [B] the live rows (1 .. T).  Row i of sequence b
+    sits at position ctx_len[b] - n_rows[b] + i and attends cache tokens 0 .. that position; rows
+    i >= n_rows[b] are padding and come out 0.  The rows' own k / v must already be in the cache
+    (:func:`rope_kv` with slots).  All three per-step tensors are read on the device, so a captured
+    launch replays for any step.  ``T * (H // Hkv) <= 64``.  Returns out [B*T, H*D]."""
+    T = int(T)
+    D = k_cache.shape[3]
+    if Hkv <= 0 or H % Hkv != 0 or H // Hkv > 16:
+        raise ValueError("paged_verify: at most 16 query heads per kv head")
+    if T < 1 or T * (H // Hkv) > PAGED_VERIFY_MAX_COLS:
+        raise ValueError(f"paged_verify: T * (H / Hkv) = {T * (H // Hkv)} exceeds {PAGED_VERIFY_MAX_COLS} columns")
+    if q.dim() != 2 or q.shape[0] % T != 0 or q.shape[1] < H * D:
+        raise ValueError("paged_verify: q must be [B*T, >= H*D]")
+    B = q.shape[0] // T
+    if block_table.dim() != 2 or block_table.shape[0] != B or ctx_len.numel() != B or n_rows.numel() != B:
+        raise ValueError("paged_verify: block_table [B, W], ctx_len [B] and n_rows [B] must match q's B")
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    if out is None:
+        out = torch.empty((B * T, H * D), device=q.device, dtype=q.dtype)
+    elif out.dim() != 2 or out.shape[0] != B * T or out.shape[1] < H * D:
+        raise ValueError("paged_verify: out must be [B*T, >= H*D]")
+    if q.is_cuda:
+        if D not in PAGED_PREFILL_HEAD_DIMS:
+            raise ValueError("paged_verify: head dim 32, 64 or 128")
+        nsplit, bps = splits if splits is not None else decode_splits(B, Hkv, block_table.shape[1])   # splits: benchmarks
+        po = pm = None
+        if nsplit > 1:
+            need = B * T * H * nsplit
+            ws = workspace if workspace is not None else {}
+            po = ws.get("vo")
+            if po is None or po.numel() < need * D:
+                po = torch.empty(need * D, device=q.device, dtype=torch.float32)
+                ws["vo"] = po
+            pm = ws.get("vml")
+            if pm is None or pm.numel() < need * 2:
+                pm = torch.empty(need * 2, device=q.device, dtype=torch.float32)
+                ws["vml"] = pm
+        hip_ops().paged_verify(q, k_cache, v_cache, block_table, ctx_len, n_rows, out, T, int(H), int(Hkv),
+                               float(scale), int(nsplit), int(bps), po, pm)
+        return out
+    G = H // Hkv
+    out[:, :H * D] = 0
+    for b in range(B):
+        L, n = int(ctx_len[b]), min(max(int(n_rows[b]), 0), T)
+        if L <= 0 or n == 0:
+            continue
+        k, v = gather_kv(k_cache, v_cache, block_table[b, :-(-L // KV_BLOCK)].long(), L)
+        k, v = k.float().permute(1, 0, 2), v.float().permute(1, 0, 2)          # [Hkv, L, D]
+        qb = q[b * T:b * T + n, :H * D].float().view(n, Hkv, G, D)
+        s = torch.einsum("thgd,hsd->hgts", qb, k) * scale
+        hidden = torch.arange(L)[None, :] > (L - n + torch.arange(n))[:, None]           # [n, L]
+        p = torch.softmax(s.masked_fill(hidden, float("-inf")), -1)
+        p = torch.nan_to_num(p)                                                # a row before position 0 sees nothing
+        o = torch.einsum("hgts,hsd->thgd", p, v)
+        out[b * T:b * T + n, :H * D] = o.reshape(n, H * D).to(out.dtype)
     return out
 
 

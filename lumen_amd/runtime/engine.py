@@ -17,6 +17,10 @@ host<->device every token (packages/lumen-vlm/src/lumen_vlm/backends/onnxrt_back
 * all running requests then advance together: one batched decode step per
   iteration (paged flash-decoding), sampling from on-device top-k candidates;
 * finished sequences release their blocks;
+* speculative decoding (``drafter`` / ``LUMEN_SPEC_DECODE=ngram``, off by default): when every
+  running request is greedy and unpenalised and some request has a draft, the step is a verify
+  step (:meth:`LLM.verify`) that scores the last token plus the draft tokens of every request and
+  emits the agreeing prefix plus one token -- the same tokens in fewer steps;
 * prefix reuse (``submit(prefix_keys=...)`` / :meth:`LLMEngine.match_prefix`): a prompt whose
   leading 64-token blocks carry the content keys of an earlier prompt starts from that prompt's
   KV blocks and prefills only the rest (the chunk path above, ``start_pos`` = the hit); a prompt
@@ -47,6 +51,7 @@ from ..ops import llm as lops
 from ..parallel.comm import TPGroupUnavailable
 from ..utils.h2d import h2d, h2d_ahead
 from .kv_cache import BLOCK, PagedKVCache
+from .spec_decode import Drafter, NgramDrafter, drafter_from_env, spec_tokens_from_env  # noqa: F401
 
 log = logging.getLogger("lumen.engine")
 
@@ -87,6 +92,10 @@ class GenRequest:
     seen_n: int = 0                         # ... tokens[:seen_n] are marked in it by the steps launched so far
     us: dict = field(default_factory=dict)  # ... token index -> its uniform, drawn once in token order
     u_next: int = -1                        # ... first token index whose uniform is not drawn yet
+    prompt_ids: Any = None                  # speculative decoding: the prompt's token ids, if the caller gave them
+    hist: Optional[list] = None             # ... prompt ids + tokens, as the drafter sees them
+    hist0: int = 0                          # ... prompt ids in hist
+    draft: tuple = (-1, ())                 # ... (len(tokens) it was made for, proposal)
 
     def stream(self, timeout: Optional[float] = None) -> Iterator[tuple]:
         """yields ("token", id) ... then ("done", reason) | raises the engine error."""
@@ -400,6 +409,12 @@ class DecodeGraphs:
     supplies, so sampled and penalised requests replay and look ahead like greedy ones.  Their step
     buffer also carries per-row 1/T, top_p, penalty, greedy flag, bitmap slot and uniform; their
     result buffer is the tokens plus the error word.  Padded rows are greedy with slot -1.
+
+    ``mode="verify"`` graphs (speculative decoding, single GPU; again with buffers of their own)
+    run :meth:`LLM.verify` over T rows per sequence, at most 32 rows in all: the step buffer carries
+    token ids, positions and slots of Bp * T rows and context length, live-row count and block
+    table of Bp sequences; the result buffer is the arg-max token of every row plus the error
+    word.  Padded rows use slot -1; padded sequences context 1 with one live row.
     """
 
     BUCKETS = (1, 2, 4, 8, 16, 32, 64, 128)
@@ -492,6 +507,26 @@ class DecodeGraphs:
             self._stream = ops.private_stream(d)
         return self._stream
 
+    def _record(self, run, d: torch.device):
+        """Warm ``run`` up twice on the private stream, then capture it; returns (graph, run's result)."""
+        s = self._capture_stream(d)
+        s.wait_stream(torch.cuda.current_stream(d))
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                run()
+        torch.cuda.current_stream(d).wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        if self.pool is None:
+            self.pool = torch.cuda.graph_pool_handle()
+        # captured on the warm-up stream: the split-K tickets / workspaces the kernels key by stream
+        # already exist (a first request inside the capture would record its zero-fill into every replay)
+        # thread_local: a multi-service engine process runs other services' batch loops on other
+        # threads meanwhile; the default (global) mode would fail their HIP calls during the capture
+        # (ops.CAPTURE_LOCK: one capture at a time in the process, see there)
+        with ops.CAPTURE_LOCK, torch.cuda.graph(g, pool=self.pool, stream=s, capture_error_mode="thread_local"):
+            out = run()
+        return g, out
+
     def _capture(self, Bp: int, W: int, mode: str = "greedy") -> dict:
         d = self.llm.embed.device
         sample = mode == "sample"
@@ -568,22 +603,7 @@ class DecodeGraphs:
                 ids.copy_(i[:, 0])                                   # greedy next token, on the device
             return logits
 
-        s = self._capture_stream(d)
-        s.wait_stream(torch.cuda.current_stream(d))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                run()
-        torch.cuda.current_stream(d).wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        if self.pool is None:
-            self.pool = torch.cuda.graph_pool_handle()
-        # captured on the warm-up stream: the split-K tickets / workspaces the kernels key by stream
-        # already exist (a first request inside the capture would record its zero-fill into every replay)
-        # thread_local: a multi-service engine process runs other services' batch loops on other
-        # threads meanwhile; the default (global) mode would fail their HIP calls during the capture
-        # (ops.CAPTURE_LOCK: one capture at a time in the process, see there)
-        with ops.CAPTURE_LOCK, torch.cuda.graph(g, pool=self.pool, stream=s, capture_error_mode="thread_local"):
-            out = run()
+        g, out = self._record(run, d)
         pin = lambda t: torch.empty(t.shape, dtype=t.dtype).pin_memory()  # noqa: E731
         ent = {"g": g, "st": st, "dbuf": dbuf, "out": out, "ws": ws, "res": res, "lay": lay, "Bp": Bp, "W": W,
                "h_step": [pin(dbuf) for _ in range(2)], "h_ids": [pin(ids) for _ in range(2)],
@@ -660,6 +680,107 @@ class DecodeGraphs:
         h["err"] = int(r[e["Bp"]])
         return r[:B]
 
+    # ---- verify mode (speculative decoding): up to T rows per sequence, single GPU
+    def verify_bucket(self, B: int, T: int) -> int:
+        """padded sequence count of a verify step: the batch bucket while its rows fit the 32-row
+        decode GEMMs, else the largest count that does"""
+        Bp = self._bucket(B)
+        return Bp if Bp * T <= 32 else 32 // T
+
+    @staticmethod
+    def _layout_verify(Bp: int, W: int, T: int) -> dict:
+        """byte offsets of (slots i64, ids i64, pos i32: Bp * T rows; ctx, n_rows, bt i32: Bp sequences)"""
+        R = Bp * T
+        o_ids = 8 * R
+        o_pos = o_ids + 8 * R
+        o_ctx = o_pos + 4 * R
+        o_n = o_ctx + 4 * Bp
+        o_bt = o_n + 4 * Bp
+        return {"slots": (0, R), "ids": (o_ids, R), "pos": (o_pos, R), "ctx": (o_ctx, Bp), "n_rows": (o_n, Bp),
+                "bt": (o_bt, Bp * W), "bytes": -(-(o_bt + 4 * Bp * W) // 16) * 16}
+
+    def _capture_verify(self, Bp: int, W: int, T: int) -> dict:
+        d = self.llm.embed.device
+        lay = self._layout_verify(Bp, W, T)
+        R, k = Bp * T, self.K_GREEDY
+        dbuf = torch.zeros(lay["bytes"], dtype=torch.uint8, device=d)
+
+        def views(buf):
+            v = {}
+            for name, dt in (("slots", torch.int64), ("ids", torch.int64), ("pos", torch.int32),
+                             ("ctx", torch.int32), ("n_rows", torch.int32), ("bt", torch.int32)):
+                o, n = lay[name]
+                v[name] = buf[o:o + dt.itemsize * n].view(dt)
+            v["bt"] = v["bt"].view(Bp, W)
+            return v
+
+        st = views(dbuf)
+        st["slots"].fill_(-1)
+        st["ctx"].fill_(1)
+        st["n_rows"].fill_(1)
+        res = torch.zeros(R + 1, dtype=torch.int32, device=d)          # arg-max token per row + the error word
+        cand = torch.zeros(2 * R * k + R, dtype=torch.float32, device=d)
+        ws: dict = {}
+
+        def run():
+            logits = self.llm.verify(st["ids"], st["pos"], st["slots"], self.kv, st["bt"], st["ctx"], st["n_rows"], T,
+                                     workspace=ws)
+            i = cand[R * k:2 * R * k].view(torch.int32).view(R, k)
+            ops.hip_ops().row_topk(logits, k, 1.0, cand[:R * k].view(R, k), i, cand[2 * R * k:], int(self.llm.v0))
+            res[:R].copy_(i[:, 0])
+            return logits
+
+        g, out = self._record(run, d)
+        pin = lambda t: torch.empty(t.shape, dtype=t.dtype).pin_memory()  # noqa: E731
+        ent = {"g": g, "st": st, "dbuf": dbuf, "out": out, "ws": ws, "res": res, "lay": lay, "Bp": Bp, "W": W, "T": T,
+               "h_step": [pin(dbuf) for _ in range(2)], "h_res": [pin(res) for _ in range(2)],
+               "ev": [None, None], "par": 0, "mode": "verify"}
+        ent["h_views"] = [views(h) for h in ent["h_step"]]
+        self.graphs[(Bp, W, "verify")] = ent
+        return ent
+
+    def _entry_verify(self, B: int, width: int, T: int) -> dict:
+        key = (self.verify_bucket(B, T), self._width(width), "verify")
+        e = self.graphs.get(key)
+        return e if e is not None and e["T"] == T else self._capture_verify(key[0], key[1], T)
+
+    def launch_verify(self, ids, pos, slots, bt, ctx, n_rows, T: int) -> dict:
+        """Stage + replay one verify step: ids / pos / slots host arrays of B * T rows
+        (sequence-major, padding rows slot -1), ctx / n_rows of B sequences.  Returns a handle
+        for :meth:`verified`."""
+        B = len(ctx)
+        e = self._entry_verify(B, bt.shape[1], T)
+        W = e["W"]
+        par = e["par"]
+        e["par"] ^= 1
+        if e["ev"][par] is not None:
+            e["ev"][par].synchronize()        # the copies that last used these pinned buffers are done
+        hv = {k: v.numpy() for k, v in e["h_views"][par].items()}
+        w = min(bt.shape[1], W)
+        for k, pad, val in (("slots", -1, slots), ("ids", 0, ids), ("pos", 0, pos)):
+            hv[k][:] = pad
+            hv[k][:B * T] = val
+        for k, val in (("ctx", ctx), ("n_rows", n_rows)):
+            hv[k][:] = 1
+            hv[k][:B] = val
+        hv["bt"][:] = 0
+        hv["bt"][:B, :w] = bt[:, :w]
+        e["dbuf"].copy_(e["h_step"][par], non_blocking=True)
+        e["g"].replay()
+        e["h_res"][par].copy_(e["res"], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        e["ev"][par] = ev
+        return {"e": e, "par": par, "B": B, "ev": ev}
+
+    def verified(self, h: dict) -> np.ndarray:
+        """arg-max tokens [B * T] int32 of a launched verify step (waits for it); sets ``h["err"]``"""
+        e = h["e"]
+        h["ev"].synchronize()
+        r = e["h_res"][h["par"]].numpy()
+        h["err"] = int(r[e["Bp"] * e["T"]])
+        return r[:h["B"] * e["T"]]
+
     def run(self, ids, pos, slots, bt, ctx) -> torch.Tensor:
         """Replay one step and return its logits [B, V/tp] (device, valid until the next replay)."""
         h = self.launch(ids, pos, slots, bt, ctx)
@@ -670,12 +791,17 @@ class LLMEngine:
     def __init__(self, llm, kv: PagedKVCache, prefill_builder: Callable[[Any], torch.Tensor], max_batch: int = 64,
                  max_prefill_per_step: int = 4, tp_sync: Optional[TPSync] = None, name: str = "vlm",
                  use_graphs: Optional[bool] = None, prefill_chunk: Optional[int] = None,
-                 follower_args: Optional[Callable[[Any], Any]] = None, ingraph_sampling: Optional[bool] = None):
+                 follower_args: Optional[Callable[[Any], Any]] = None, ingraph_sampling: Optional[bool] = None,
+                 spec_tokens: Optional[int] = None, drafter: Optional[Drafter] = None):
         """``follower_args``: what the TP followers receive instead of the prefill arguments
         (the VLM strips the image: only rank 0 decodes it and runs the vision tower).
         ``ingraph_sampling``: sampled / penalised requests decode through the graphs' device
         sampler with look-ahead (single GPU; None: env ``LUMEN_INGRAPH_SAMPLING``, default on).
-        Off: they take the synchronous host path, as they always do under TP and without graphs."""
+        Off: they take the synchronous host path, as they always do under TP and without graphs.
+        ``drafter`` (``callable(token_ids, k) -> list[int]``; None: env ``LUMEN_SPEC_DECODE=ngram``
+        gives :class:`NgramDrafter`, default off): speculative decoding of greedy requests, with
+        ``spec_tokens`` draft tokens per verify step (None: env ``LUMEN_SPEC_TOKENS``, default 3,
+        1 .. 7)."""
         self.llm = llm
         self.kv = kv
         self.build = prefill_builder
@@ -693,7 +819,8 @@ class LLMEngine:
         self._pending: Optional[tuple] = None     # (request ids, handle) of a look-ahead decode step in flight
         self.device = llm.embed.device
         self.stats = {"prefills": 0, "prefill_chunks": 0, "decode_steps": 0, "tokens": 0,
-                      "prefix_hits": 0, "prefix_tokens": 0, "prefill_tokens": 0}
+                      "prefix_hits": 0, "prefix_tokens": 0, "prefill_tokens": 0,
+                      "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
         if use_graphs is None:
             use_graphs = os.environ.get("LUMEN_HIP_GRAPHS", "1") == "1"
         self.graphs: Optional[DecodeGraphs] = None
@@ -707,6 +834,8 @@ class LLMEngine:
         if ingraph_sampling is None:
             ingraph_sampling = os.environ.get("LUMEN_INGRAPH_SAMPLING", "1") != "0"
         self.ingraph_sampling = bool(ingraph_sampling) and tp_sync is None and not llm.tp.enabled
+        self.drafter = drafter if drafter is not None else drafter_from_env()
+        self.spec_T = spec_tokens_from_env(spec_tokens) + 1      # rows per sequence of a verify step
         self._thread = threading.Thread(target=self._loop, name=f"lumen-{name}-engine", daemon=True)
         self._thread.start()
 
@@ -737,12 +866,14 @@ class LLMEngine:
             hit.tokens = 0
 
     def submit(self, prefill_args: Any, prompt_len: int, params: SamplingParams, prefix_keys=None,
-               hit: Optional[PrefixHit] = None) -> GenRequest:
+               hit: Optional[PrefixHit] = None, prompt_ids: Optional[Sequence[int]] = None) -> GenRequest:
         """``prefix_keys``: uint64 [n, 2], key i covering prompt tokens [64 i, 64 i + 64) and chaining
         key i - 1 -- the prompt may start from cached blocks and publishes its own after prefill.
         ``hit``: the result of an earlier :meth:`match_prefix` with the same keys (the request
         takes over its id and references).  The prefill builder must return all ``prompt_len``
-        rows; rows before the hit are never read."""
+        rows; rows before the hit are never read.
+        ``prompt_ids``: the prompt's token ids for the speculative-decoding drafter (without them
+        it sees the generated tokens only)."""
         try:
             if self._stop.is_set():
                 raise RuntimeError("engine stopped")
@@ -766,7 +897,7 @@ class LLMEngine:
                 hit.tokens = self.kv.blocks.match(keys[:self._hit_cap(prompt_len)], hit.rid)
         r = GenRequest(rid=hit.rid, prefill_args=prefill_args, prompt_len=prompt_len, params=params,
                        t_submit=time.perf_counter(), rng=np.random.default_rng(params.seed),
-                       cached_tokens=hit.tokens, prefix_keys=keys)
+                       cached_tokens=hit.tokens, prefix_keys=keys, prompt_ids=prompt_ids)
         self._waiting.put(r)
         return r
 
@@ -1011,10 +1142,106 @@ class LLMEngine:
                 return False
         return True
 
+    # ------------------------------------------------------------------ speculative decoding
+    def _spec_ok(self, reqs) -> bool:
+        """a verify step may serve this batch: a drafter is set, single GPU without a step channel,
+        every request greedy without repetition penalty, and B * T rows fit the 32-row decode GEMMs"""
+        return (self.drafter is not None and self.sync is None and not self.llm.tp.enabled
+                and len(reqs) * self.spec_T <= 32
+                and all(r.params.temperature <= 0 and not self._penalised(r) for r in reqs))
+
+    def _draft(self, r: GenRequest) -> tuple:
+        """the drafter's proposal for ``r``'s next tokens, cut so that the request neither exceeds
+        ``max_new_tokens`` (the step also yields one token of its own) nor leaves its reserved blocks;
+        made once per generated length"""
+        n = len(r.tokens)
+        if r.draft[0] == n:
+            return r.draft[1]
+        k = min(self.spec_T - 1, r.params.max_new_tokens - n - 1,
+                len(self.kv.blocks.table(r.rid)) * BLOCK - r.ctx - 1)
+        d: tuple = ()
+        if k > 0:
+            if r.hist is None:
+                r.hist = [int(t) for t in r.prompt_ids] if r.prompt_ids is not None else []
+                r.hist0 = len(r.hist)
+            r.hist.extend(r.tokens[len(r.hist) - r.hist0:])
+            d = tuple(int(t) for t in self.drafter(r.hist, k))[:k]
+        r.draft = (n, d)
+        return d
+
+    def _spec_drafts(self, reqs) -> Optional[list]:
+        """per-request drafts if the next step of ``reqs`` is a verify step (some draft is non-empty)"""
+        if not self._spec_ok(reqs):
+            return None
+        drafts = [self._draft(r) for r in reqs]
+        return drafts if any(drafts) else None
+
+    @torch.no_grad()
+    def _verify(self, reqs, drafts) -> None:
+        """One verify step: sequence b feeds tokens[-1] and its draft as rows b*T .. at positions
+        ctx ..; row i's arg-max is the model's token after row i's input, so draft i is accepted while
+        it equals the arg-max of row i - 1, and the arg-maxes of rows 0 .. (accepted) are emitted.
+        Rejected rows' cache entries lie beyond the new ctx and are rewritten when next fed."""
+        T, B = self.spec_T, len(reqs)
+        ids = np.zeros(B * T, np.int64)
+        pos = np.zeros(B * T, np.int32)
+        slots = np.full(B * T, -1, np.int64)
+        n_rows = np.array([1 + len(d) for d in drafts], np.int32)
+        ctx = np.array([r.ctx for r in reqs], np.int32) + n_rows
+        for b, (r, d) in enumerate(zip(reqs, drafts)):
+            n, o = 1 + len(d), b * T
+            ids[o] = r.tokens[-1]
+            ids[o + 1:o + n] = d
+            pos[o:o + n] = r.ctx + np.arange(n)
+            slots[o:o + n] = self.kv.slots(r.rid, r.ctx, n)
+        bt = self.kv.block_table([r.rid for r in reqs])
+        am = None
+        if self.graphs is not None and bt.shape[1] <= self.graphs.max_blocks:
+            try:
+                h = self.graphs.launch_verify(ids, pos, slots, bt, ctx, n_rows, T)
+                am = self.graphs.verified(h)
+            except Exception as e:  # noqa: BLE001 - capture unsupported: eager launches from now on
+                log.warning("hipGraph decode disabled: %s", e)
+                self.graphs = None
+        if am is None:
+            d = self.device
+            logits = self.llm.verify(h2d(ids, d), h2d(pos, d), h2d(slots, d), self.kv, h2d(bt, d), h2d(ctx, d),
+                                     h2d(n_rows, d), T, workspace=self._ws)
+            _v, i, _lse = ops.row_topk(logits, DecodeGraphs.K_GREEDY, with_lse=True, index_offset=self.llm.v0)
+            am = i[:, 0].cpu().numpy()
+        self.stats["spec_steps"] += 1
+        still = []
+        for b, (r, d) in enumerate(zip(reqs, drafts)):
+            row = am[b * T:b * T + 1 + len(d)]
+            j = 0
+            while j < len(d) and d[j] == int(row[j]):
+                j += 1
+            self.stats["spec_drafted"] += len(d)
+            self.stats["spec_accepted"] += j
+            done = False
+            for t in row[:j + 1]:
+                r.ctx += 1
+                if self._emit(r, int(t)):
+                    done = True
+                    break
+            if done:
+                self._finish(r)
+            else:
+                still.append(r)
+        self._running = still
+
     @torch.no_grad()
     def _decode(self) -> None:
         reqs = self._running
         B = len(reqs)
+        # a look-ahead step in flight for this batch is consumed below by the usual rules; otherwise a
+        # batch with a draft takes a verify step
+        if self._pending is None or self._pending[0] != [r.rid for r in reqs]:
+            drafts = self._spec_drafts(reqs)
+            if drafts is not None:
+                self._pending = None
+                self._verify(reqs, drafts)
+                return
         spec = Sampler.spec(reqs)
         mode = "greedy" if self._greedy_graph_ok(reqs, spec) else "sample" if self._sample_graph_ok(reqs, spec) \
             else None
@@ -1032,7 +1259,10 @@ class LLMEngine:
                 h = self._launch_greedy(ids, self._step_inputs(reqs, 0), spec,
                                         self._sample_inputs(reqs, 0, True) if smp else None)
             nxt = None
-            if self._can_look_ahead(reqs):
+            # with a drafter the next step may be a verify step, known only once this step's tokens
+            # are read: the look-ahead is then launched after them, and only if nothing was drafted
+            late = self._spec_ok(reqs)
+            if not late and self._can_look_ahead(reqs):
                 nxt = self._launch_greedy(None, self._step_inputs(reqs, 1), spec,
                                           self._sample_inputs(reqs, 1, False) if smp else None)
             if smp:
@@ -1054,6 +1284,9 @@ class LLMEngine:
                 else:
                     still.append(r)
             self._running = still
+            if late and len(still) == B and self._can_look_ahead(reqs) and self._spec_drafts(reqs) is None:
+                nxt = self._launch_greedy(np.array([r.tokens[-1] for r in reqs], np.int64),
+                                          self._step_inputs(reqs, 0), spec)      # ctx already advanced
             if nxt is not None and len(still) == B:
                 self._pending = (rids, nxt)
                 self.stats["lookahead_steps"] = self.stats.get("lookahead_steps", 0) + 1

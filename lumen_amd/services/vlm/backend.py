@@ -642,7 +642,8 @@ class MI355XVLMBackend:
         sp = SamplingParams(max_new_tokens=max(1, int(req.max_new_tokens)), temperature=float(req.temperature),
                             top_p=float(req.top_p), repetition_penalty=float(req.repetition_penalty),
                             stop_token_ids=tuple(stops), seed=req.extra.get("seed"))
-        r = self.engine.submit((ids, img if starts else None), len(full), sp, prefix_keys=keys, hit=hit)
+        r = self.engine.submit((ids, img if starts else None), len(full), sp, prefix_keys=keys, hit=hit,
+                               prompt_ids=full)
         if hit is not None:
             hit.tokens = 0      # the request owns the references now
         return r

@@ -183,7 +183,9 @@ def main():
     sampling = {"temperature": args.temperature, "top_p": args.top_p, "repetition_penalty": args.repetition_penalty,
                 "seed": args.seed, "ingraph": eng.ingraph_sampling,
                 "ingraph_sample_steps": eng.stats.get("ingraph_sample_steps", 0),
-                "lookahead_steps": eng.stats.get("lookahead_steps", 0), "decode_steps": eng.stats["decode_steps"]}
+                "lookahead_steps": eng.stats.get("lookahead_steps", 0), "decode_steps": eng.stats["decode_steps"],
+                "spec_steps": eng.stats["spec_steps"], "spec_drafted": eng.stats["spec_drafted"],
+                "spec_accepted": eng.stats["spec_accepted"]}
     out = {"metric": "VLM p50 TTFT", "value": float(np.percentile(ttft, 50)), "unit": "ms",
            "higher_is_better": False, "p90_ttft_ms": float(np.percentile(ttft, 90)),
            "p99_ttft_ms": float(np.percentile(ttft, 99)),
