@@ -301,6 +301,68 @@ void sample_rows(const at::Tensor& logits, const at::Tensor& inv_t, const at::Te
   CHECK_HIP3(lumen::sample_rows(a, nws > 0 ? ws.data_ptr<float>() : nullptr, cur()));
 }
 
+// The sampler's verify form (speculative decoding): logits f32 [B * T, V], row b * T + i = input i of
+// sequence b, live while i < n_rows[b].  inv_t / top_p / penalty / greedy / seen_slot are per
+// sequence [B]; u, in_ids and tok per row [B * T].  Row (b, i) is penalised over b's bitmap slot and
+// in_ids[b * T .. b * T + i]; tok of a dead row is -1.  verify_accept then writes n_acc int32 [B]
+// and marks in_ids[b * T .. b * T + n_acc[b]] in the slot -- the draw itself marks nothing.
+void sample_verify_rows(const at::Tensor& logits, int64_t T, const at::Tensor& n_rows, const at::Tensor& inv_t,
+                        const at::Tensor& top_p, const at::Tensor& penalty, const at::Tensor& u,
+                        const at::Tensor& greedy, const at::Tensor& seen_slot, at::Tensor seen,
+                        const at::Tensor& in_ids, at::Tensor tok, at::Tensor n_acc,
+                        const c10::optional<at::Tensor>& out_v, const c10::optional<at::Tensor>& out_i,
+                        const c10::optional<at::Tensor>& out_lse) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat && logits.dim() == 2 && logits.stride(1) == 1,
+              "sample_verify_rows: logits f32 [B * T, V]");
+  const int64_t R = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= lumen::SAMPLE_K && V < (int64_t(1) << 31), "sample_verify_rows: V >= 64");
+  TORCH_CHECK(T >= 1 && T <= lumen::SAMPLE_VERIFY_MAX_T && R % T == 0, "sample_verify_rows: T in 1 .. 8, rows = B * T");
+  const int64_t B = R / T;
+  TORCH_CHECK(B <= 64, "sample_verify_rows: at most 64 sequences");
+  auto vec = [&](const at::Tensor& t, at::ScalarType ty, int64_t n, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == ty && t.is_contiguous() && t.numel() == n &&
+                t.device() == logits.device(), "sample_verify_rows: ", what);
+  };
+  vec(n_rows, at::kInt, B, "n_rows int32 [B]");
+  vec(inv_t, at::kFloat, B, "inv_t f32 [B]");
+  vec(top_p, at::kDouble, B, "top_p f64 [B]");
+  vec(penalty, at::kFloat, B, "penalty f32 [B]");
+  vec(greedy, at::kInt, B, "greedy int32 [B]");
+  vec(seen_slot, at::kInt, B, "seen_slot int32 [B]");
+  vec(n_acc, at::kInt, B, "n_acc int32 [B]");
+  vec(u, at::kDouble, R, "u f64 [B * T]");
+  vec(in_ids, at::kLong, R, "in_ids int64 [B * T]");
+  vec(tok, at::kInt, R, "tok int32 [B * T]");
+  const int64_t words = (V + 31) / 32;
+  TORCH_CHECK(seen.is_cuda() && seen.scalar_type() == at::kInt && seen.is_contiguous() && seen.dim() == 2 &&
+              seen.size(1) == words && seen.device() == logits.device(),
+              "sample_verify_rows: seen int32 [S, ceil(V / 32)]");
+  lumen::SampleArgs a{};
+  a.logits = logits.data_ptr<float>(); a.ld = logits.stride(0);
+  a.B = (int)B; a.V = (int)V; a.T = (int)T;
+  a.n_rows = n_rows.data_ptr<int>(); a.n_acc = n_acc.data_ptr<int>();
+  a.inv_t = inv_t.data_ptr<float>(); a.top_p = top_p.data_ptr<double>(); a.penalty = penalty.data_ptr<float>();
+  a.u = u.data_ptr<double>(); a.greedy = greedy.data_ptr<int>(); a.seen_slot = seen_slot.data_ptr<int>();
+  a.seen = seen.data_ptr<int>(); a.S = (int)seen.size(0); a.words = (int)words;
+  a.in_ids = in_ids.data_ptr<int64_t>(); a.tok = tok.data_ptr<int>();
+  const bool cand = out_v.has_value() && out_v->defined();
+  TORCH_CHECK(cand == (out_i.has_value() && out_i->defined()), "sample_verify_rows: out_v and out_i come together");
+  if (cand) {
+    vec(*out_v, at::kFloat, R * lumen::SAMPLE_K, "out_v f32 [B * T, 64]");
+    vec(*out_i, at::kInt, R * lumen::SAMPLE_K, "out_i int32 [B * T, 64]");
+    a.out_v = out_v->data_ptr<float>(); a.out_i = out_i->data_ptr<int>();
+  }
+  if (out_lse.has_value() && out_lse->defined()) {
+    vec(*out_lse, at::kFloat, R, "out_lse f32 [B * T]");
+    a.out_lse = out_lse->data_ptr<float>();
+  }
+  const at::DeviceGuard g(logits.device());
+  const int64_t nws = lumen::sample_ws_floats((int)R, (int)V);
+  at::Tensor ws;
+  if (nws > 0) ws = at::empty({nws}, logits.options());
+  CHECK_HIP3(lumen::sample_rows(a, nws > 0 ? ws.data_ptr<float>() : nullptr, cur()));
+}
+
 // int32 CPU values -> int64 device tensor through the kernel arguments (llm.hip:upload_i64)
 void upload_small(const at::Tensor& src, at::Tensor out) {
   TORCH_CHECK(!src.is_cuda() && src.scalar_type() == at::kInt && src.is_contiguous(), "upload_small: src int32 CPU");
@@ -333,6 +395,9 @@ TORCH_LIBRARY_FRAGMENT(lumen, m) {
   m.def("sample_rows(Tensor logits, Tensor inv_t, Tensor top_p, Tensor penalty, Tensor u, Tensor greedy, "
         "Tensor seen_slot, Tensor(s!) seen, Tensor in_ids, Tensor(o!) out_ids, Tensor(t!) tok, "
         "Tensor(v!)? out_v=None, Tensor(i!)? out_i=None, Tensor(l!)? out_lse=None) -> ()");
+  m.def("sample_verify_rows(Tensor logits, int T, Tensor n_rows, Tensor inv_t, Tensor top_p, Tensor penalty, Tensor u, "
+        "Tensor greedy, Tensor seen_slot, Tensor(s!) seen, Tensor in_ids, Tensor(t!) tok, Tensor(n!) n_acc, "
+        "Tensor(v!)? out_v=None, Tensor(i!)? out_i=None, Tensor(l!)? out_lse=None) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(lumen, CUDA, m) {
@@ -344,4 +409,5 @@ TORCH_LIBRARY_IMPL(lumen, CUDA, m) {
   m.impl("upload_small", &upload_small);
   m.impl("decode_set_dbg", &decode_set_dbg);
   m.impl("sample_rows", &sample_rows);
+  m.impl("sample_verify_rows", &sample_verify_rows);
 }

@@ -7,6 +7,7 @@
 namespace lumen {
 
 constexpr int SAMPLE_K = 64;   // candidates per row = one wave
+constexpr int SAMPLE_VERIFY_MAX_T = 8;   // rows per sequence of the verify form
 
 struct SampleArgs {
   const float* logits;      // [B, V] rows of stride ld; read only
@@ -26,9 +27,16 @@ struct SampleArgs {
   float* out_v;             // optional [B, 64] candidate values (transformed logits, descending)
   int* out_i;               // optional [B, 64] candidate token ids
   float* out_lse;           // optional [B] log-sum-exp of the transformed row
+  // Verify form (speculative decoding), T > 0: logits, u, in_ids, tok and the optional outputs have
+  // B * T rows, row b * T + i = input i of sequence b; everything else stays per sequence [B].
+  // in_ids of a sequence are its last token and its draft tokens; out_ids is unused.  T = 0: the
+  // decode form above.
+  int T;
+  const int* n_rows;        // [B] live rows of each sequence (a dead row writes tok = -1 only)
+  int* n_acc;               // [B] out: accepted draft tokens; in_ids 0 .. n_acc are marked in the slot
 };
 
-// floats of workspace sample_rows needs for B rows of V columns (0: single launch)
+// floats of workspace sample_rows needs for B rows (the verify form: B * T) of V columns (0: single launch)
 int64_t sample_ws_floats(int B, int V);
 hipError_t sample_rows(const SampleArgs& a, float* ws, hipStream_t stream);
 

@@ -19,6 +19,17 @@
 // A greedy row needs its best candidate only: unless the caller asked for the candidates, its
 // workgroups run one merge round instead of 64 (the rounds, two barriers each, are most of the
 // sampler's time on a vocabulary-sized row).
+//
+// Verify form (SampleArgs.T > 0, speculative decoding): R = B * T rows, sequence-major; row (b, i)
+// holds the logits after sequence b's input i (its last token, then its draft tokens) and is live
+// while i < n_rows[b] (a dead row only writes tok = -1).  The per-sequence arguments are read at
+// b, the uniform and the input token at the row.  The penalty set of row (b, i) is b's bitmap slot
+// and inputs 0 .. i of b: those are OR-ed into the LDS copy of the bitmap chunk before the scan, so
+// the per-element test stays the one bit test, and the floating-point operations and the order of
+// the candidates are the decode form's.  A verify row marks nothing: verify_accept, one launch
+// behind the draw, finds per sequence the number of draft tokens that equal the token drawn for the
+// row before them and marks the inputs up to the last accepted one -- a rejected draft token never
+// reaches the bitmap.
 #include "sampler.h"
 
 #include "topk_core.h"
@@ -61,17 +72,26 @@ enum : int { SAMPLE_PARTIAL = 0, SAMPLE_SINGLE = 1, SAMPLE_MERGE = 2 };
 // PARTIAL: grid (B, chunks), transformed candidates + (max, sum-exp) of one chunk -> workspace.
 // SINGLE:  grid (B, 1), the whole row in one workgroup, then the draw.
 // MERGE:   grid (B, 1), the chunks' candidates and statistics merged, then the draw.
-template <int MODE>
+// VERIFY: row = (sequence seq, input vi) of the verify form; else seq = row.
+template <int MODE, bool VERIFY>
 __global__ void __launch_bounds__(256)
 sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__ ci, float* __restrict__ pml,
                    int nch) {
   __shared__ int bits[SAMPLE_STAGE_WORDS];
   const int row = blockIdx.x;
-  const int slot_in = a.seen_slot[row];
+  const int seq = VERIFY ? row / a.T : row, vi = VERIFY ? row % a.T : 0;
+  if constexpr (VERIFY) {
+    if (vi >= a.n_rows[seq]) {   // a dead row: the whole workgroup leaves (the merge never reads its partials)
+      if (MODE != SAMPLE_PARTIAL && threadIdx.x == 0) a.tok[row] = -1;
+      return;
+    }
+  }
+  const int slot_in = a.seen_slot[seq];
   const int slot = slot_in < a.S ? slot_in : -1;
   const int64_t in64 = a.in_ids[row];
-  const int in_id = in64 >= 0 && in64 < a.V ? (int)in64 : -1;
-  const int k = a.greedy[row] && !a.out_v ? 1 : SAMPLE_K;
+  // verify: the inputs up to the row's own are bits of the staged bitmap, not a compare per element
+  const int in_id = !VERIFY && in64 >= 0 && in64 < a.V ? (int)in64 : -1;
+  const int k = a.greedy[seq] && !a.out_v ? 1 : SAMPLE_K;
   float lse0;
   LaneSink lanes{-INFINITY, -1, a.out_v, a.out_i, (int64_t)row * SAMPLE_K};
   if constexpr (MODE == SAMPLE_MERGE) {
@@ -80,13 +100,25 @@ sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__
   } else {
     const int chunk = MODE == SAMPLE_PARTIAL ? TOPK_CHUNK : a.V;
     const int j0 = blockIdx.y * chunk, j1 = min(a.V, j0 + chunk);
-    SeenXf xf{bits, j0, in_id, a.penalty[row], a.inv_t[row], false};
+    SeenXf xf{bits, j0, in_id, a.penalty[seq], a.inv_t[seq], false};
     xf.on = slot >= 0 && xf.pen != 1.f;
     if (xf.on) {
       const int* srow = a.seen + (int64_t)slot * a.words + (j0 >> 5);
       const int nw = min((j1 - j0 + 31) >> 5, SAMPLE_STAGE_WORDS);
       for (int t = threadIdx.x; t < nw; t += 256) bits[t] = srow[t];
       __syncthreads();
+      if constexpr (VERIFY) {
+        if (threadIdx.x == 0) {   // at most T ids, two of which may share a word: one thread, in turn
+          for (int q = 0; q <= vi; ++q) {
+            const int64_t id = a.in_ids[row - vi + q];
+            if (id >= j0 && id < j1) {
+              const int r = (int)id - j0;
+              if ((r >> 5) < nw) bits[r >> 5] |= (int)(1u << (r & 31));
+            }
+          }
+        }
+        __syncthreads();
+      }
     }
     if constexpr (MODE == SAMPLE_PARTIAL) {
       TopkStore store{cv, ci, ((int64_t)row * gridDim.y + blockIdx.y) * SAMPLE_K, 0};
@@ -110,20 +142,44 @@ sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__
     const double pi = __shfl(p, i, 64);
     if (i <= lane) c += pi;
   }
-  const double top_p = a.top_p[row], ctot = __shfl(c, SAMPLE_K - 1, 64);
+  const double top_p = a.top_p[seq], ctot = __shfl(c, SAMPLE_K - 1, 64);
   const double thr = ctot < top_p ? top_p * ctot : top_p;
   const int n = min(max(__popcll(__ballot(c < thr)) + 1, 1), SAMPLE_K);
   const double cn = __shfl(c, n - 1, 64);
   int js = min(__popcll(__ballot(lane < n && c / cn <= a.u[row])), n - 1);
-  if (a.greedy[row]) js = 0;
+  if (a.greedy[seq]) js = 0;
   const int t = __shfl(lanes.i, js, 64);
   if (lane == 0) {
     a.tok[row] = t;
-    a.out_ids[row] = t < 0 ? 0 : t;      // a row without a finite logit must not index the embedding with -1
-    if (slot >= 0 && in_id >= 0) {       // a slot belongs to one row: plain read-modify-write
-      int* w = a.seen + (int64_t)slot * a.words + (in_id >> 5);
-      *w = *w | (int)(1u << (in_id & 31));
+    if constexpr (!VERIFY) {
+      a.out_ids[row] = t < 0 ? 0 : t;    // a row without a finite logit must not index the embedding with -1
+      if (slot >= 0 && in_id >= 0) {     // a slot belongs to one row: plain read-modify-write
+        int* w = a.seen + (int64_t)slot * a.words + (in_id >> 5);
+        *w = *w | (int)(1u << (in_id & 31));
+      }
     }
+  }
+}
+
+// One wave, lane b = sequence b (B <= 64; the verify form has at most 32 rows): n_acc[b] = the
+// draft tokens of b that equal the token drawn for the row before them, up to the first that does
+// not; inputs 0 .. n_acc[b] (the last token and the accepted draft tokens) are marked in b's slot.
+// A slot belongs to one sequence and a lane marks its ids in turn: plain read-modify-write.
+__global__ void __launch_bounds__(64) verify_accept_kernel(const SampleArgs a) {
+  const int b = threadIdx.x;
+  if (b >= a.B) return;
+  const int n = min(a.n_rows[b], a.T);
+  const int* tok = a.tok + (int64_t)b * a.T;
+  const int64_t* in = a.in_ids + (int64_t)b * a.T;
+  int j = 0;
+  while (j < n - 1 && (int64_t)tok[j] == in[j + 1]) ++j;
+  a.n_acc[b] = j;
+  const int slot = a.seen_slot[b];
+  if (n <= 0 || slot < 0 || slot >= a.S) return;
+  int* srow = a.seen + (int64_t)slot * a.words;
+  for (int q = 0; q <= j; ++q) {
+    const int64_t id = in[q];
+    if (id >= 0 && id < a.V) srow[id >> 5] |= (int)(1u << ((int)id & 31));
   }
 }
 
@@ -132,24 +188,37 @@ int64_t sample_ws_floats(int B, int V) {
   return nch > 1 ? (int64_t)B * nch * (2 * SAMPLE_K + 2) : 0;
 }
 
-hipError_t sample_rows(const SampleArgs& a, float* ws, hipStream_t stream) {
-  if (a.B == 0) return hipSuccess;
-  if (a.V < SAMPLE_K || a.words != (a.V + 31) / 32) return hipErrorInvalidValue;
+// the draw of R rows (the decode form: R = a.B; the verify form: R = a.B * a.T)
+template <bool VERIFY>
+static hipError_t launch_rows(const SampleArgs& a, int R, float* ws, hipStream_t stream) {
   const int nch = topk_chunks(a.V);
   if (nch == 1) {
     if (a.words > SAMPLE_STAGE_WORDS) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sample_rows_kernel<SAMPLE_SINGLE>, dim3(a.B, 1), dim3(256), 0, stream, a, nullptr, nullptr,
-                       nullptr, 1);
+    hipLaunchKernelGGL((sample_rows_kernel<SAMPLE_SINGLE, VERIFY>), dim3(R, 1), dim3(256), 0, stream, a, nullptr,
+                       nullptr, nullptr, 1);
     return hipGetLastError();
   }
   if (ws == nullptr) return hipErrorInvalidValue;
   float* cv = ws;
-  int* ci = reinterpret_cast<int*>(ws + (int64_t)a.B * nch * SAMPLE_K);
-  float* pml = ws + (int64_t)a.B * nch * SAMPLE_K * 2;
-  hipLaunchKernelGGL(sample_rows_kernel<SAMPLE_PARTIAL>, dim3(a.B, nch), dim3(256), 0, stream, a, cv, ci, pml, nch);
+  int* ci = reinterpret_cast<int*>(ws + (int64_t)R * nch * SAMPLE_K);
+  float* pml = ws + (int64_t)R * nch * SAMPLE_K * 2;
+  hipLaunchKernelGGL((sample_rows_kernel<SAMPLE_PARTIAL, VERIFY>), dim3(R, nch), dim3(256), 0, stream, a, cv, ci, pml,
+                     nch);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(sample_rows_kernel<SAMPLE_MERGE>, dim3(a.B, 1), dim3(256), 0, stream, a, cv, ci, pml, nch);
+  hipLaunchKernelGGL((sample_rows_kernel<SAMPLE_MERGE, VERIFY>), dim3(R, 1), dim3(256), 0, stream, a, cv, ci, pml, nch);
+  return hipGetLastError();
+}
+
+hipError_t sample_rows(const SampleArgs& a, float* ws, hipStream_t stream) {
+  if (a.B == 0) return hipSuccess;
+  if (a.V < SAMPLE_K || a.words != (a.V + 31) / 32) return hipErrorInvalidValue;
+  if (a.T == 0) return launch_rows<false>(a, a.B, ws, stream);
+  if (a.T < 1 || a.T > SAMPLE_VERIFY_MAX_T || a.B > 64 || a.n_rows == nullptr || a.n_acc == nullptr)
+    return hipErrorInvalidValue;
+  hipError_t e = launch_rows<true>(a, a.B * a.T, ws, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(verify_accept_kernel, dim3(1), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -394,3 +394,84 @@ def sample_rows(logits: torch.Tensor, inv_t, top_p, penalty, u, greedy, seen_slo
             seen[slot, feed[b] >> 5] |= bit - (1 << 32) if bit >> 31 else bit
     out_ids.copy_(tok.long())
     return v, i.to(torch.int32), lse, tok, seen
+
+
+SAMPLE_VERIFY_MAX_T = 8      # rows per sequence of the sampler's verify form (csrc/sampler.h)
+
+
+def _mark_seen(seen: torch.Tensor, slot: int, t: int) -> None:
+    bit = 1 << (t & 31)
+    seen[slot, t >> 5] |= bit - (1 << 32) if bit >> 31 else bit
+
+
+def sample_verify_rows(logits: torch.Tensor, T: int, n_rows, inv_t, top_p, penalty, u, greedy, seen_slot,
+                       seen: torch.Tensor, in_ids, candidates: bool = True):
+    """The verify form of :func:`sample_rows` (speculative decoding of sampled / penalised requests):
+    fp32 ``logits`` [B * T, V], row ``b * T + i`` holding the logits after input ``i`` of sequence ``b``
+    -- ``in_ids[b * T]`` is its last token, the next ones its draft tokens -- and live while
+    ``i < n_rows[b]``.
+
+    ``inv_t``, ``top_p``, ``penalty``, ``greedy`` and ``seen_slot`` are per sequence [B]; ``u`` and
+    ``in_ids`` per row [B * T].  Row (b, i) is penalised over the bitmap slot of b and
+    ``in_ids[b * T .. b * T + i]`` (not the later inputs) and drawn as :func:`sample_rows` draws;
+    a dead row gives ``tok = -1``.  The draw marks nothing.  ``n_acc[b]`` is the number of leading
+    draft tokens that equal the token of the row before them (``tok[b*T + i] == in_ids[b*T + i + 1]``),
+    and ``in_ids[b * T .. b * T + n_acc[b]]`` -- the tokens that really were fed -- are marked in
+    the slot (a slot of -1 or beyond ``seen`` marks nothing).
+
+    Returns ``(v [B*T, 64], i [B*T, 64], lse [B*T], tok [B*T] int32, n_acc [B] int32, seen)``; dead
+    rows of ``v, i, lse`` are unspecified on the GPU (-inf, -1, 0 on the CPU).  ``candidates=False``
+    on the GPU: ``v, i, lse`` are None.  CPU tensors run the reference of :func:`sample_rows` row
+    by row."""
+    d = logits.device
+    T = int(T)
+    R, V = logits.shape
+    if V < SAMPLE_K:
+        raise ValueError(f"sample_verify_rows: V >= {SAMPLE_K}")
+    if not 1 <= T <= SAMPLE_VERIFY_MAX_T:
+        raise ValueError(f"sample_verify_rows: T in 1 .. {SAMPLE_VERIFY_MAX_T}")
+    B = torch.as_tensor(n_rows).numel()
+    if R != B * T:
+        raise ValueError(f"sample_verify_rows: {R} rows of logits for B * T = {B} * {T}")
+    as_t = lambda x, dt, n: torch.as_tensor(x, dtype=dt, device=d).reshape(n).contiguous()  # noqa: E731
+    n_rows = as_t(n_rows, torch.int32, B)
+    inv_t, penalty = as_t(inv_t, torch.float32, B), as_t(penalty, torch.float32, B)
+    top_p, u = as_t(top_p, torch.float64, B), as_t(u, torch.float64, R)
+    greedy, seen_slot = as_t(greedy, torch.int32, B), as_t(seen_slot, torch.int32, B)
+    in_ids = as_t(in_ids, torch.long, R)
+    if logits.is_cuda:
+        tok = torch.empty(R, dtype=torch.int32, device=d)
+        n_acc = torch.empty(B, dtype=torch.int32, device=d)
+        v = torch.empty((R, SAMPLE_K), dtype=torch.float32, device=d) if candidates else None
+        i = torch.empty((R, SAMPLE_K), dtype=torch.int32, device=d) if candidates else None
+        lse = torch.empty(R, dtype=torch.float32, device=d) if candidates else None
+        hip_ops().sample_verify_rows(logits, T, n_rows, inv_t, top_p, penalty, u, greedy, seen_slot, seen, in_ids,
+                                     tok, n_acc, v, i, lse)
+        return v, i, lse, tok, n_acc, seen
+    v = torch.full((R, SAMPLE_K), float("-inf"))
+    i = torch.full((R, SAMPLE_K), -1, dtype=torch.int32)
+    lse = torch.zeros(R)
+    tok = torch.full((R,), -1, dtype=torch.int32)
+    n_acc = torch.zeros(B, dtype=torch.int32)
+    feed = in_ids.tolist()
+    for b in range(B):
+        n = min(int(n_rows[b]), T)
+        slot = int(seen_slot[b])
+        own = 0 <= slot < seen.shape[0]
+        # the row's penalty set grows by one input per row: a scratch copy of the slot, which
+        # sample_rows marks with the row's input after it drew -- the real bitmap is not touched
+        tmp = seen[slot:slot + 1].clone() if own else seen[:0]
+        for q in range(n):
+            r = b * T + q
+            rv, ri, rl, rt, tmp = sample_rows(logits[r:r + 1], inv_t[b:b + 1], top_p[b:b + 1], penalty[b:b + 1],
+                                              u[r:r + 1], greedy[b:b + 1], [0 if own else -1], tmp, in_ids[r:r + 1])
+            v[r], i[r], lse[r], tok[r] = rv[0], ri[0], rl[0], rt[0]
+        j = 0
+        while j < n - 1 and int(tok[b * T + j]) == feed[b * T + j + 1]:
+            j += 1
+        n_acc[b] = j
+        if own and n > 0:
+            for t in feed[b * T:b * T + j + 1]:
+                if 0 <= t < V:
+                    _mark_seen(seen, slot, t)
+    return v, i, lse, tok, n_acc, seen

@@ -20,7 +20,9 @@ host<->device every token (packages/lumen-vlm/src/lumen_vlm/backends/onnxrt_back
 * speculative decoding (``drafter`` / ``LUMEN_SPEC_DECODE=ngram``, off by default): when every
   running request is greedy and unpenalised and some request has a draft, the step is a verify
   step (:meth:`LLM.verify`) that scores the last token plus the draft tokens of every request and
-  emits the agreeing prefix plus one token -- the same tokens in fewer steps;
+  emits the agreeing prefix plus one token -- the same tokens in fewer steps; with
+  ``spec_sampling`` / ``LUMEN_SPEC_SAMPLING=1`` sampled and penalised requests take part, every
+  row's token drawn by the device sampler's verify form with the uniform of its position;
 * prefix reuse (``submit(prefix_keys=...)`` / :meth:`LLMEngine.match_prefix`): a prompt whose
   leading 64-token blocks carry the content keys of an earlier prompt starts from that prompt's
   KV blocks and prefills only the rest (the chunk path above, ``start_pos`` = the hit); a prompt
@@ -166,11 +168,22 @@ class Sampler:
             i = torch.gather(ids, 1, order).to(torch.int32)
         return v, i, lse
 
-    def pick(self, cands, reqs: Sequence[GenRequest]) -> list[int]:
+    def pick(self, cands, reqs: Sequence[GenRequest], uniform: Optional[Callable] = None) -> list[int]:
+        """``uniform(r, n)``: the engine's per-request uniform stream.  A request that has drawn from
+        it (``u_next >= 0``: a device-sampled or verify step ran) takes token n's value from there,
+        by the device sampler's rule -- ``Generator.choice`` would draw a fresh one and leave the
+        stream's order."""
         v, i, lse = (t.cpu().numpy() for t in cands)
         out = []
         for b, r in enumerate(reqs):
-            if r.params.temperature > 0:
+            if r.params.temperature > 0 and uniform is not None and r.u_next >= 0:
+                c = np.cumsum(np.exp(v[b].astype(np.float64) - np.float64(lse[b])))
+                tp = float(r.params.top_p)
+                n = int(np.searchsorted(c, tp * c[-1] if c[-1] < tp else tp) + 1)
+                n = max(1, min(n, len(c)))
+                j = min(n - 1, int(np.searchsorted(c[:n] / c[n - 1], uniform(r, len(r.tokens)), side="right")))
+                out.append(int(i[b, j]))
+            elif r.params.temperature > 0:
                 out.append(lops.sample_from_candidates(v[b], i[b], float(lse[b]), r.params.temperature,
                                                        r.params.top_p, r.rng))
             else:
@@ -379,7 +392,42 @@ def tp_sync_capacity(max_batch: int, max_position: int) -> int:
     return max_batch * (4 + -(-max_position // 64))
 
 
-class DecodeGraphs:
+class SeenSlots:
+    """The device sampler's seen-token bitmaps: [max_batch, ceil(V / 32)] int32 (19 KB per row at
+    V = 151,936), one row = "slot" per penalised request, allocated on first use.  :class:`DecodeGraphs`
+    is one; an engine without graphs that samples verify steps holds a bare one."""
+
+    def __init__(self, llm, max_batch: int):
+        self.llm = llm
+        self.max_batch = max(max_batch, 1)
+        self.seen: Optional[torch.Tensor] = None
+        self._free_slots = list(range(self.max_batch - 1, -1, -1))
+
+    def _seen(self) -> torch.Tensor:
+        if self.seen is None:
+            self.seen = torch.zeros((self.max_batch, lops.seen_words(self.llm.Vl)), dtype=torch.int32,
+                                    device=self.llm.embed.device)
+        return self.seen
+
+    def take_slot(self) -> Optional[int]:
+        """a free row of the seen bitmap (None: all taken); fill it with :meth:`write_slot`"""
+        return self._free_slots.pop() if self._free_slots else None
+
+    def free_slot(self, slot: int) -> None:
+        self._free_slots.append(slot)
+
+    def write_slot(self, slot: int, tokens: Sequence[int]) -> None:
+        """Set row ``slot`` of the bitmap to exactly ``tokens`` (none: zero it), on the current
+        stream -- the one the graphs replay on, so it lands after every step launched before."""
+        seen = self._seen()
+        row = np.zeros(seen.shape[1], np.uint32)
+        t = np.asarray([x for x in tokens if 0 <= x < self.llm.Vl], np.int64)
+        if len(t):
+            np.bitwise_or.at(row, t >> 5, np.uint32(1) << (t & 31).astype(np.uint32))
+        seen[slot].copy_(torch.from_numpy(row.view(np.int32)))
+
+
+class DecodeGraphs(SeenSlots):
     """hipGraph-captured decode steps, one graph per (padded batch-size, table-width) bucket.
 
     A decode step is ~5 kernels per layer (hundreds per token) whose host launch cost
@@ -415,13 +463,21 @@ class DecodeGraphs:
     token ids, positions and slots of Bp * T rows and context length, live-row count and block
     table of Bp sequences; the result buffer is the arg-max token of every row plus the error
     word.  Padded rows use slot -1; padded sequences context 1 with one live row.
+
+    ``mode="verify_sample"`` graphs are the verify step with the device sampler's verify form
+    (``sample_verify_rows``: the draw of every row, then ``verify_accept``) in place of the row
+    arg-max, for batches with sampled or penalised requests.  The step buffer also carries the
+    sampler's per-sequence rows (as in ``sample`` mode) and one uniform per row; the result buffer is
+    the drawn token of every row, the accepted draft tokens of every sequence and the error word.
+    Padded sequences are greedy with slot -1 and one live row.
     """
 
     BUCKETS = (1, 2, 4, 8, 16, 32, 64, 128)
     K_GREEDY = 8
 
     def __init__(self, llm, kv: PagedKVCache, max_batch: int, max_blocks: int):
-        self.llm, self.kv = llm, kv
+        SeenSlots.__init__(self, llm, max_batch)     # sample / verify_sample modes: the seen-token bitmaps
+        self.kv = kv
         self.max_blocks = max_blocks
         self.buckets = [b for b in self.BUCKETS if b <= max(max_batch, 1)] or [1]
         if self.buckets[-1] < max_batch:
@@ -431,10 +487,6 @@ class DecodeGraphs:
         self.pool = None
         self.in_graph_sampler = not llm.tp.enabled or os.environ.get("LUMEN_TP_INGRAPH_SAMPLER", "1") == "1"
         self._stream = None     # the capture stream, private to this instance (see _capture_stream)
-        # sample mode: seen-token bitmaps [max_batch, ceil(V / 32)] int32 (19 KB per row at V = 151,936)
-        self.max_batch = max(max_batch, 1)
-        self.seen: Optional[torch.Tensor] = None
-        self._free_slots = list(range(self.max_batch - 1, -1, -1))
 
     def _bucket(self, B: int) -> int:
         for b in self.buckets:
@@ -474,29 +526,6 @@ class DecodeGraphs:
     _SAMPLE_ROWS = {"u": torch.float64, "top_p": torch.float64, "inv_t": torch.float32, "penalty": torch.float32,
                     "greedy": torch.int32, "seen_slot": torch.int32}
     _SAMPLE_PAD = {"u": 0.0, "top_p": 1.0, "inv_t": 1.0, "penalty": 1.0, "greedy": 1, "seen_slot": -1}
-
-    def _seen(self) -> torch.Tensor:
-        if self.seen is None:
-            self.seen = torch.zeros((self.max_batch, lops.seen_words(self.llm.Vl)), dtype=torch.int32,
-                                    device=self.llm.embed.device)
-        return self.seen
-
-    def take_slot(self) -> Optional[int]:
-        """a free row of the seen bitmap (None: all taken); fill it with :meth:`write_slot`"""
-        return self._free_slots.pop() if self._free_slots else None
-
-    def free_slot(self, slot: int) -> None:
-        self._free_slots.append(slot)
-
-    def write_slot(self, slot: int, tokens: Sequence[int]) -> None:
-        """Set row ``slot`` of the bitmap to exactly ``tokens`` (none: zero it), on the current
-        stream -- the one the graphs replay on, so it lands after every step launched before."""
-        seen = self._seen()
-        row = np.zeros(seen.shape[1], np.uint32)
-        t = np.asarray([x for x in tokens if 0 <= x < self.llm.Vl], np.int64)
-        if len(t):
-            np.bitwise_or.at(row, t >> 5, np.uint32(1) << (t & 31).astype(np.uint32))
-        seen[slot].copy_(torch.from_numpy(row.view(np.int32)))
 
     def _capture_stream(self, d: torch.device) -> torch.cuda.Stream:
         """One stream per engine that nothing else ever uses.  The split-K tickets and
@@ -699,9 +728,25 @@ class DecodeGraphs:
         return {"slots": (0, R), "ids": (o_ids, R), "pos": (o_pos, R), "ctx": (o_ctx, Bp), "n_rows": (o_n, Bp),
                 "bt": (o_bt, Bp * W), "bytes": -(-(o_bt + 4 * Bp * W) // 16) * 16}
 
-    def _capture_verify(self, Bp: int, W: int, T: int) -> dict:
+    @staticmethod
+    def _layout_verify_sample(Bp: int, W: int, T: int) -> dict:
+        """the verify layout followed by the sampler's rows: u f64 of Bp * T rows, then (top_p f64,
+        inv_t f32, penalty f32, greedy i32, seen_slot i32) of Bp sequences; the f64 rows start
+        16-byte aligned"""
+        lay = dict(DecodeGraphs._layout_verify(Bp, W, T))
+        o = lay["bytes"]
+        for k, sz, n in (("u", 8, Bp * T), ("top_p", 8, Bp), ("inv_t", 4, Bp), ("penalty", 4, Bp), ("greedy", 4, Bp),
+                         ("seen_slot", 4, Bp)):
+            lay[k] = (o, n)
+            o += sz * n
+        lay["bytes"] = -(-o // 16) * 16
+        return lay
+
+    def _capture_verify(self, Bp: int, W: int, T: int, sample: bool = False) -> dict:
+        """``sample``: the ``verify_sample`` graph -- the device sampler's verify form and its accept
+        kernel in place of the row arg-max; ``res`` = tok [Bp * T], n_acc [Bp] and the error word"""
         d = self.llm.embed.device
-        lay = self._layout_verify(Bp, W, T)
+        lay = self._layout_verify_sample(Bp, W, T) if sample else self._layout_verify(Bp, W, T)
         R, k = Bp * T, self.K_GREEDY
         dbuf = torch.zeros(lay["bytes"], dtype=torch.uint8, device=d)
 
@@ -712,44 +757,64 @@ class DecodeGraphs:
                 o, n = lay[name]
                 v[name] = buf[o:o + dt.itemsize * n].view(dt)
             v["bt"] = v["bt"].view(Bp, W)
+            if sample:
+                for name, dt in self._SAMPLE_ROWS.items():
+                    o, n = lay[name]
+                    v[name] = buf[o:o + dt.itemsize * n].view(dt)
             return v
 
         st = views(dbuf)
         st["slots"].fill_(-1)
         st["ctx"].fill_(1)
         st["n_rows"].fill_(1)
-        res = torch.zeros(R + 1, dtype=torch.int32, device=d)          # arg-max token per row + the error word
-        cand = torch.zeros(2 * R * k + R, dtype=torch.float32, device=d)
         ws: dict = {}
+        if sample:
+            for name, pad in self._SAMPLE_PAD.items():
+                st[name].fill_(pad)
+            res = torch.zeros(R + Bp + 1, dtype=torch.int32, device=d)
+            seen = self._seen()
 
-        def run():
-            logits = self.llm.verify(st["ids"], st["pos"], st["slots"], self.kv, st["bt"], st["ctx"], st["n_rows"], T,
-                                     workspace=ws)
-            i = cand[R * k:2 * R * k].view(torch.int32).view(R, k)
-            ops.hip_ops().row_topk(logits, k, 1.0, cand[:R * k].view(R, k), i, cand[2 * R * k:], int(self.llm.v0))
-            res[:R].copy_(i[:, 0])
-            return logits
+            def run():
+                logits = self.llm.verify(st["ids"], st["pos"], st["slots"], self.kv, st["bt"], st["ctx"], st["n_rows"],
+                                         T, workspace=ws)
+                ops.hip_ops().sample_verify_rows(logits, T, st["n_rows"], st["inv_t"], st["top_p"], st["penalty"],
+                                                 st["u"], st["greedy"], st["seen_slot"], seen, st["ids"], res[:R],
+                                                 res[R:R + Bp], None, None, None)
+                return logits
+        else:
+            res = torch.zeros(R + 1, dtype=torch.int32, device=d)          # arg-max token per row + the error word
+            cand = torch.zeros(2 * R * k + R, dtype=torch.float32, device=d)
+
+            def run():
+                logits = self.llm.verify(st["ids"], st["pos"], st["slots"], self.kv, st["bt"], st["ctx"], st["n_rows"],
+                                         T, workspace=ws)
+                i = cand[R * k:2 * R * k].view(torch.int32).view(R, k)
+                ops.hip_ops().row_topk(logits, k, 1.0, cand[:R * k].view(R, k), i, cand[2 * R * k:], int(self.llm.v0))
+                res[:R].copy_(i[:, 0])
+                return logits
 
         g, out = self._record(run, d)
         pin = lambda t: torch.empty(t.shape, dtype=t.dtype).pin_memory()  # noqa: E731
+        mode = "verify_sample" if sample else "verify"
         ent = {"g": g, "st": st, "dbuf": dbuf, "out": out, "ws": ws, "res": res, "lay": lay, "Bp": Bp, "W": W, "T": T,
                "h_step": [pin(dbuf) for _ in range(2)], "h_res": [pin(res) for _ in range(2)],
-               "ev": [None, None], "par": 0, "mode": "verify"}
+               "ev": [None, None], "par": 0, "mode": mode}
         ent["h_views"] = [views(h) for h in ent["h_step"]]
-        self.graphs[(Bp, W, "verify")] = ent
+        self.graphs[(Bp, W, mode)] = ent
         return ent
 
-    def _entry_verify(self, B: int, width: int, T: int) -> dict:
-        key = (self.verify_bucket(B, T), self._width(width), "verify")
+    def _entry_verify(self, B: int, width: int, T: int, sample: bool = False) -> dict:
+        key = (self.verify_bucket(B, T), self._width(width), "verify_sample" if sample else "verify")
         e = self.graphs.get(key)
-        return e if e is not None and e["T"] == T else self._capture_verify(key[0], key[1], T)
+        return e if e is not None and e["T"] == T else self._capture_verify(key[0], key[1], T, sample)
 
-    def launch_verify(self, ids, pos, slots, bt, ctx, n_rows, T: int) -> dict:
+    def launch_verify(self, ids, pos, slots, bt, ctx, n_rows, T: int, sample: Optional[dict] = None) -> dict:
         """Stage + replay one verify step: ids / pos / slots host arrays of B * T rows
         (sequence-major, padding rows slot -1), ctx / n_rows of B sequences.  Returns a handle
-        for :meth:`verified`."""
+        for :meth:`verified`.  ``sample``: the device sampler's arrays (keys of ``_SAMPLE_ROWS``;
+        ``u`` of B * T rows, the others of B sequences) -- the step runs the ``verify_sample`` graph."""
         B = len(ctx)
-        e = self._entry_verify(B, bt.shape[1], T)
+        e = self._entry_verify(B, bt.shape[1], T, sample is not None)
         W = e["W"]
         par = e["par"]
         e["par"] ^= 1
@@ -765,6 +830,10 @@ class DecodeGraphs:
             hv[k][:B] = val
         hv["bt"][:] = 0
         hv["bt"][:B, :w] = bt[:, :w]
+        if sample is not None:
+            for k, pad in self._SAMPLE_PAD.items():
+                hv[k][:] = pad
+                hv[k][:len(sample[k])] = sample[k]
         e["dbuf"].copy_(e["h_step"][par], non_blocking=True)
         e["g"].replay()
         e["h_res"][par].copy_(e["res"], non_blocking=True)
@@ -774,11 +843,18 @@ class DecodeGraphs:
         return {"e": e, "par": par, "B": B, "ev": ev}
 
     def verified(self, h: dict) -> np.ndarray:
-        """arg-max tokens [B * T] int32 of a launched verify step (waits for it); sets ``h["err"]``"""
+        """tokens [B * T] int32 of a launched verify step -- the arg-max of every row, or what the
+        ``verify_sample`` graph drew (then ``h["n_acc"]`` holds the device's accepted counts [B]) --
+        (waits for it); sets ``h["err"]``"""
         e = h["e"]
         h["ev"].synchronize()
         r = e["h_res"][h["par"]].numpy()
-        h["err"] = int(r[e["Bp"] * e["T"]])
+        R = e["Bp"] * e["T"]
+        if e["mode"] == "verify_sample":
+            h["n_acc"] = r[R:R + h["B"]]
+            h["err"] = int(r[R + e["Bp"]])
+        else:
+            h["err"] = int(r[R])
         return r[:h["B"] * e["T"]]
 
     def run(self, ids, pos, slots, bt, ctx) -> torch.Tensor:
@@ -792,7 +868,8 @@ class LLMEngine:
                  max_prefill_per_step: int = 4, tp_sync: Optional[TPSync] = None, name: str = "vlm",
                  use_graphs: Optional[bool] = None, prefill_chunk: Optional[int] = None,
                  follower_args: Optional[Callable[[Any], Any]] = None, ingraph_sampling: Optional[bool] = None,
-                 spec_tokens: Optional[int] = None, drafter: Optional[Drafter] = None):
+                 spec_tokens: Optional[int] = None, drafter: Optional[Drafter] = None,
+                 spec_sampling: Optional[bool] = None):
         """``follower_args``: what the TP followers receive instead of the prefill arguments
         (the VLM strips the image: only rank 0 decodes it and runs the vision tower).
         ``ingraph_sampling``: sampled / penalised requests decode through the graphs' device
@@ -801,7 +878,9 @@ class LLMEngine:
         ``drafter`` (``callable(token_ids, k) -> list[int]``; None: env ``LUMEN_SPEC_DECODE=ngram``
         gives :class:`NgramDrafter`, default off): speculative decoding of greedy requests, with
         ``spec_tokens`` draft tokens per verify step (None: env ``LUMEN_SPEC_TOKENS``, default 3,
-        1 .. 7)."""
+        1 .. 7).
+        ``spec_sampling`` (None: env ``LUMEN_SPEC_SAMPLING=1``, default off): batches with sampled
+        or penalised requests take verify steps too, drawn by the device sampler's verify form."""
         self.llm = llm
         self.kv = kv
         self.build = prefill_builder
@@ -820,7 +899,7 @@ class LLMEngine:
         self.device = llm.embed.device
         self.stats = {"prefills": 0, "prefill_chunks": 0, "decode_steps": 0, "tokens": 0,
                       "prefix_hits": 0, "prefix_tokens": 0, "prefill_tokens": 0,
-                      "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
+                      "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0, "spec_sample_steps": 0}
         if use_graphs is None:
             use_graphs = os.environ.get("LUMEN_HIP_GRAPHS", "1") == "1"
         self.graphs: Optional[DecodeGraphs] = None
@@ -836,6 +915,14 @@ class LLMEngine:
         self.ingraph_sampling = bool(ingraph_sampling) and tp_sync is None and not llm.tp.enabled
         self.drafter = drafter if drafter is not None else drafter_from_env()
         self.spec_T = spec_tokens_from_env(spec_tokens) + 1      # rows per sequence of a verify step
+        if spec_sampling is None:
+            spec_sampling = os.environ.get("LUMEN_SPEC_SAMPLING", "0") == "1"
+        self.spec_sampling = bool(spec_sampling) and tp_sync is None and not llm.tp.enabled
+        # the seen-token bitmaps: the graphs' own (kept if a capture failure drops the graphs), or
+        # a bare set for sampled verify steps without graphs
+        self._slots: Optional[SeenSlots] = self.graphs
+        if self._slots is None and self.spec_sampling and self.drafter is not None:
+            self._slots = SeenSlots(llm, max_batch)
         self._thread = threading.Thread(target=self._loop, name=f"lumen-{name}-engine", daemon=True)
         self._thread.start()
 
@@ -933,16 +1020,18 @@ class LLMEngine:
     def _join(self, r: GenRequest) -> None:
         """``r`` enters the running batch; a penalised request takes a zeroed row of the device
         sampler's seen bitmap (none free, or no graphs: its batches sample on the host)"""
-        if self.ingraph_sampling and self.graphs is not None and self._penalised(r):
-            r.seen_slot = self.graphs.take_slot()
+        wanted = (self.ingraph_sampling and self.graphs is not None) or \
+            (self.spec_sampling and self.drafter is not None and self._slots is not None)
+        if wanted and self._penalised(r):
+            r.seen_slot = self._slots.take_slot()
             if r.seen_slot is not None:
-                self.graphs.write_slot(r.seen_slot, r.tokens[:-1])
+                self._slots.write_slot(r.seen_slot, r.tokens[:-1])
                 r.seen_n = len(r.tokens) - 1
         self._running.append(r)
 
     def _drop_slot(self, r: GenRequest) -> None:
-        if r.seen_slot is not None and self.graphs is not None:
-            self.graphs.free_slot(r.seen_slot)
+        if r.seen_slot is not None and self._slots is not None:
+            self._slots.free_slot(r.seen_slot)
         r.seen_slot = None
 
     def _finish(self, r: GenRequest) -> None:
@@ -1068,10 +1157,11 @@ class LLMEngine:
                 and len(reqs) <= g.buckets[-1] and self.llm.Vl >= lops.SAMPLE_K
                 and all(r.seen_slot is not None for r in reqs if self._penalised(r)))
 
-    def _uniform(self, r: GenRequest, n: int) -> float:
+    def _uniform(self, r: GenRequest, n: int, base: Optional[int] = None) -> float:
         """the uniform of token ``n`` of ``r``: ``r.rng.random()``, which is what the host path's
         ``Generator.choice`` draws for it -- once, in token order, kept for a step that is launched
-        again after a discarded look-ahead"""
+        again after a discarded look-ahead or that follows a verify step whose rows drew ahead
+        (``base``: the first token of such a step; values from ``base - 1`` on are kept)"""
         if r.params.temperature <= 0:
             return 0.0
         if r.u_next < 0:
@@ -1079,20 +1169,21 @@ class LLMEngine:
         while r.u_next <= n:
             r.us[r.u_next] = float(r.rng.random())
             r.u_next += 1
-        r.us.pop(n - 2, None)
+        lo = (n if base is None else base) - 1
+        for k in [k for k in r.us if k < lo]:
+            del r.us[k]
         return r.us[n]
 
     def _sample_inputs(self, reqs, ahead: int, fed: bool) -> dict:
         """per-row inputs of the device sampler for the step that yields token len(tokens) + ahead;
         ``fed``: the step gets its input tokens from the host (not a look-ahead)"""
-        g = self.graphs
         for r in reqs:
             if r.seen_slot is None:
                 continue
             n = len(r.tokens)
             if fed:
                 if r.seen_n not in (n - 1, n):    # steps of this request ran elsewhere: rebuild its row
-                    g.write_slot(r.seen_slot, r.tokens[:-1])
+                    self._slots.write_slot(r.seen_slot, r.tokens[:-1])
                 r.seen_n = n                      # this step marks tokens[-1]
             else:
                 r.seen_n = n + 1                  # ... and this one the token the step before it draws
@@ -1145,10 +1236,21 @@ class LLMEngine:
     # ------------------------------------------------------------------ speculative decoding
     def _spec_ok(self, reqs) -> bool:
         """a verify step may serve this batch: a drafter is set, single GPU without a step channel,
-        every request greedy without repetition penalty, and B * T rows fit the 32-row decode GEMMs"""
-        return (self.drafter is not None and self.sync is None and not self.llm.tp.enabled
-                and len(reqs) * self.spec_T <= 32
-                and all(r.params.temperature <= 0 and not self._penalised(r) for r in reqs))
+        every request greedy without repetition penalty, and B * T rows fit the 32-row decode GEMMs.
+        With ``spec_sampling`` sampled and penalised requests may take part: the vocabulary holds the
+        sampler's 64 candidates and every penalised request holds a bitmap slot"""
+        if not (self.drafter is not None and self.sync is None and not self.llm.tp.enabled
+                and len(reqs) * self.spec_T <= 32):
+            return False
+        if not self._spec_sampled(reqs):
+            return True
+        return (self.spec_sampling and self._slots is not None and self.llm.Vl >= lops.SAMPLE_K
+                and self.spec_T <= lops.SAMPLE_VERIFY_MAX_T
+                and all(r.seen_slot is not None for r in reqs if self._penalised(r)))
+
+    def _spec_sampled(self, reqs) -> bool:
+        """some request is sampled or penalised: a verify step of this batch is the sampled form"""
+        return any(r.params.temperature > 0 or self._penalised(r) for r in reqs)
 
     def _draft(self, r: GenRequest) -> tuple:
         """the drafter's proposal for ``r``'s next tokens, cut so that the request neither exceeds
@@ -1176,13 +1278,41 @@ class LLMEngine:
         drafts = [self._draft(r) for r in reqs]
         return drafts if any(drafts) else None
 
+    def _verify_sample_inputs(self, reqs) -> dict:
+        """per-sequence inputs of the sampler's verify form and one uniform per row: row i of a
+        request yields its token len(tokens) + i.  Brings every bitmap slot to tokens[:-1] (a slot
+        that also holds tokens[-1], marked by a discarded look-ahead step, is as good: row 0
+        penalises that token anyway and the accept kernel marks it)."""
+        T = self.spec_T
+        for r in reqs:
+            n = len(r.tokens)
+            if r.seen_slot is not None and r.seen_n not in (n - 1, n):
+                self._slots.write_slot(r.seen_slot, r.tokens[:-1])
+                r.seen_n = n - 1
+        ps = [r.params for r in reqs]
+        return {"inv_t": np.array([1.0 / p.temperature if p.temperature > 0 else 1.0 for p in ps], np.float32),
+                "top_p": np.array([p.top_p for p in ps], np.float64),
+                "penalty": np.array([float(p.repetition_penalty) if r.seen_slot is not None else 1.0
+                                     for p, r in zip(ps, reqs)], np.float32),
+                "greedy": np.array([p.temperature <= 0 for p in ps], np.int32),
+                "seen_slot": np.array([-1 if r.seen_slot is None else r.seen_slot for r in reqs], np.int32),
+                "u": np.array([self._uniform(r, len(r.tokens) + i, len(r.tokens)) for r in reqs for i in range(T)],
+                              np.float64)}
+
     @torch.no_grad()
     def _verify(self, reqs, drafts) -> None:
         """One verify step: sequence b feeds tokens[-1] and its draft as rows b*T .. at positions
         ctx ..; row i's arg-max is the model's token after row i's input, so draft i is accepted while
         it equals the arg-max of row i - 1, and the arg-maxes of rows 0 .. (accepted) are emitted.
-        Rejected rows' cache entries lie beyond the new ctx and are rewritten when next fed."""
+        Rejected rows' cache entries lie beyond the new ctx and are rewritten when next fed.
+
+        A batch with a sampled or penalised request takes the sampled form: row i's token is drawn by
+        the device sampler's verify form from the row's penalised, scaled logits with the uniform of
+        token len(tokens) + i -- what a decode step at that position would draw -- and the rule above
+        holds with "drawn token" for "arg-max".  The accept kernel marks the accepted inputs in the
+        bitmap slots; the uniforms of rejected rows stay stored for their positions."""
         T, B = self.spec_T, len(reqs)
+        smp = self._spec_sampled(reqs)
         ids = np.zeros(B * T, np.int64)
         pos = np.zeros(B * T, np.int32)
         slots = np.full(B * T, -1, np.int64)
@@ -1195,27 +1325,49 @@ class LLMEngine:
             pos[o:o + n] = r.ctx + np.arange(n)
             slots[o:o + n] = self.kv.slots(r.rid, r.ctx, n)
         bt = self.kv.block_table([r.rid for r in reqs])
-        am = None
+        sample = self._verify_sample_inputs(reqs) if smp else None
+        am = n_acc = None
         if self.graphs is not None and bt.shape[1] <= self.graphs.max_blocks:
             try:
-                h = self.graphs.launch_verify(ids, pos, slots, bt, ctx, n_rows, T)
+                h = self.graphs.launch_verify(ids, pos, slots, bt, ctx, n_rows, T, sample)
                 am = self.graphs.verified(h)
+                n_acc = h.get("n_acc")
             except Exception as e:  # noqa: BLE001 - capture unsupported: eager launches from now on
                 log.warning("hipGraph decode disabled: %s", e)
                 self.graphs = None
+                if smp:       # the failed launch may have left the bitmap rows anywhere
+                    for r in reqs:
+                        r.seen_n = -1
+                    sample = self._verify_sample_inputs(reqs)
         if am is None:
             d = self.device
             logits = self.llm.verify(h2d(ids, d), h2d(pos, d), h2d(slots, d), self.kv, h2d(bt, d), h2d(ctx, d),
                                      h2d(n_rows, d), T, workspace=self._ws)
-            _v, i, _lse = ops.row_topk(logits, DecodeGraphs.K_GREEDY, with_lse=True, index_offset=self.llm.v0)
-            am = i[:, 0].cpu().numpy()
+            if smp:
+                t = lambda k, dt: h2d(sample[k], d, dt)  # noqa: E731
+                *_, tok, acc, _seen = lops.sample_verify_rows(
+                    logits, T, h2d(n_rows, d), t("inv_t", torch.float32), t("top_p", torch.float64),
+                    t("penalty", torch.float32), t("u", torch.float64), t("greedy", torch.int32),
+                    t("seen_slot", torch.int32), self._slots._seen(), h2d(ids, d), candidates=False)
+                am, n_acc = tok.cpu().numpy(), acc.cpu().numpy()
+            else:
+                _v, i, _lse = ops.row_topk(logits, DecodeGraphs.K_GREEDY, with_lse=True, index_offset=self.llm.v0)
+                am = i[:, 0].cpu().numpy()
         self.stats["spec_steps"] += 1
+        self.stats["spec_sample_steps"] += smp
+        acc = []
+        for b, d in enumerate(drafts):
+            j = 0
+            while j < len(d) and d[j] == int(am[b * T + j]):
+                j += 1
+            acc.append(j)
+        if n_acc is not None and acc != [int(x) for x in n_acc[:B]]:      # before anything is emitted
+            raise RuntimeError(f"verify step: the device accepted {list(n_acc[:B])} draft tokens, the host {acc}")
         still = []
         for b, (r, d) in enumerate(zip(reqs, drafts)):
-            row = am[b * T:b * T + 1 + len(d)]
-            j = 0
-            while j < len(d) and d[j] == int(row[j]):
-                j += 1
+            row, j = am[b * T:b * T + 1 + len(d)], acc[b]
+            if smp:
+                r.seen_n = len(r.tokens) + j      # the accept kernel marked tokens[-1] and the accepted draft tokens
             self.stats["spec_drafted"] += len(d)
             self.stats["spec_accepted"] += j
             done = False
@@ -1286,7 +1438,8 @@ class LLMEngine:
             self._running = still
             if late and len(still) == B and self._can_look_ahead(reqs) and self._spec_drafts(reqs) is None:
                 nxt = self._launch_greedy(np.array([r.tokens[-1] for r in reqs], np.int64),
-                                          self._step_inputs(reqs, 0), spec)      # ctx already advanced
+                                          self._step_inputs(reqs, 0), spec,      # ctx already advanced
+                                          self._sample_inputs(reqs, 0, True) if smp else None)
             if nxt is not None and len(still) == B:
                 self._pending = (rids, nxt)
                 self.stats["lookahead_steps"] = self.stats.get("lookahead_steps", 0) + 1
@@ -1301,7 +1454,7 @@ class LLMEngine:
         if self.sync is not None:
             self.sync.send_decode(ids, pos, slots, bt, ctx, spec, graph)
         logits = self._decode_step(ids, pos, slots, bt, ctx, graph)
-        toks = self.sampler.pick(self.sampler.candidates(logits, spec), reqs)
+        toks = self.sampler.pick(self.sampler.candidates(logits, spec), reqs, self._uniform)
         self.stats["decode_steps"] += 1
         comm = getattr(self.llm, "comm", None)
         if comm is not None:
