@@ -34,6 +34,19 @@ struct SampleArgs {
   int T;
   const int* n_rows;        // [B] live rows of each sequence (a dead row writes tok = -1 only)
   int* n_acc;               // [B] out: accepted draft tokens; in_ids 0 .. n_acc are marked in the slot
+  // Guided form (decode form only; all null / zero when unused): a row whose grammar state s is
+  // >= 0 draws among the tokens whose bit is set in g_allow[s], and lane 0 then walks the drawn
+  // token's bytes through g_dfa from s and stores the new state.  s = g_in[b] when that is >= 0
+  // (a step fed by the host), else g_state[g_slot[b]] (a look-ahead step, straight after the step
+  // that wrote it).  g_slot[b] = -1: an unguided row of a guided batch.
+  const int* g_allow;       // [A, words] arena of allowed-token bitmaps, one row per grammar state
+  const int16_t* g_dfa;     // [A, 256] byte transitions in arena-global state ids, -1 = dead
+  const int* tok_off;       // [V + 1] CSR of the token bytes ...
+  const uint8_t* tok_dat;   // ... and the bytes
+  const int* g_slot;        // [B] row of g_state the sequence owns, or -1
+  const int* g_in;          // [B] the state fed by the host, or -1: read g_state[g_slot]
+  int* g_state;             // [g_S] the states the device keeps between look-ahead steps
+  int g_A, g_S;
 };
 
 // floats of workspace sample_rows needs for B rows (the verify form: B * T) of V columns (0: single launch)

@@ -30,7 +30,16 @@
 // behind the draw, finds per sequence the number of draft tokens that equal the token drawn for the
 // row before them and marks the inputs up to the last accepted one -- a rejected draft token never
 // reaches the bitmap.
+//
+// Guided form (template flag GUIDED, decode form only; the other instantiations are compiled as
+// before): a row with a grammar state s >= 0 stages row s of the arena of allowed-token bitmaps
+// into a second LDS array, chunked like the seen bitmap, and a logit whose bit is clear becomes
+// -inf before the penalty and the 1/T: it is never a candidate and adds nothing to the
+// log-sum-exp, so the allowed set is renormalised.  After the draw lane 0 walks the drawn token's
+// bytes through the byte DFA from s and stores the new state, which the look-ahead step reads.
 #include "sampler.h"
+
+#include <type_traits>
 
 #include "topk_core.h"
 
@@ -41,6 +50,7 @@ int topk_chunks(int N);   // topk.hip: the sampler splits rows exactly as row_to
 constexpr int SAMPLE_STAGE_WORDS = 512;   // bitmap words of the widest single-launch row (16384 columns)
 
 struct SeenXf {
+  static constexpr bool kSkipNegInf = false;
   const int* bits;   // LDS: word 0 holds columns j0 .. j0 + 31 (j0 is a multiple of 32)
   int j0, in_id;
   float pen, inv_t;
@@ -51,6 +61,21 @@ struct SeenXf {
       if (((bits[r >> 5] >> (r & 31)) & 1) || j == in_id) x = x > 0.f ? x / pen : x * pen;
     }
     return x * inv_t;
+  }
+};
+
+// the guided form: a column whose bit in the state's allow row is clear is -inf, then SeenXf
+struct GuideXf {
+  static constexpr bool kSkipNegInf = true;
+  SeenXf seen;
+  const int* allow;   // LDS: word 0 holds columns j0 .. j0 + 31
+  int mode;           // 0: unguided row, 1: test the bit, 2: nothing is allowed
+  __device__ __forceinline__ float operator()(float x, const int j) const {
+    if (mode) {
+      const int r = j - seen.j0;
+      if (mode == 2 || !((allow[r >> 5] >> (r & 31)) & 1)) return -INFINITY;
+    }
+    return seen(x, j);
   }
 };
 
@@ -73,11 +98,13 @@ enum : int { SAMPLE_PARTIAL = 0, SAMPLE_SINGLE = 1, SAMPLE_MERGE = 2 };
 // SINGLE:  grid (B, 1), the whole row in one workgroup, then the draw.
 // MERGE:   grid (B, 1), the chunks' candidates and statistics merged, then the draw.
 // VERIFY: row = (sequence seq, input vi) of the verify form; else seq = row.
-template <int MODE, bool VERIFY>
+template <int MODE, bool VERIFY, bool GUIDED = false>
 __global__ void __launch_bounds__(256)
 sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__ ci, float* __restrict__ pml,
                    int nch) {
+  static_assert(!(VERIFY && GUIDED), "the verify form is not guided");
   __shared__ int bits[SAMPLE_STAGE_WORDS];
+  __shared__ int allow[GUIDED ? SAMPLE_STAGE_WORDS : 1];   // 2 KB more in the guided form; unused (and dropped) otherwise
   const int row = blockIdx.x;
   const int seq = VERIFY ? row / a.T : row, vi = VERIFY ? row % a.T : 0;
   if constexpr (VERIFY) {
@@ -92,6 +119,19 @@ sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__
   // verify: the inputs up to the row's own are bits of the staged bitmap, not a compare per element
   const int in_id = !VERIFY && in64 >= 0 && in64 < a.V ? (int)in64 : -1;
   const int k = a.greedy[seq] && !a.out_v ? 1 : SAMPLE_K;
+  // guided: the row's slot of g_state and its grammar state (-1: unguided row; a state outside the
+  // arena allows nothing).  Every thread reads the state before the first barrier, lane 0 stores the
+  // new one after the last.
+  int gslot = -1, gs = -1;
+  if constexpr (GUIDED) {
+    gslot = a.g_slot[row];
+    if (gslot >= a.g_S) gslot = -1;
+    if (gslot >= 0) {
+      const int fed = a.g_in[row];
+      gs = fed >= 0 ? fed : a.g_state[gslot];
+      if (gs < 0 || gs >= a.g_A) gs = a.g_A;   // no such state: nothing is allowed, tok = -1
+    }
+  }
   float lse0;
   LaneSink lanes{-INFINITY, -1, a.out_v, a.out_i, (int64_t)row * SAMPLE_K};
   if constexpr (MODE == SAMPLE_MERGE) {
@@ -120,9 +160,21 @@ sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__
         __syncthreads();
       }
     }
+    std::conditional_t<GUIDED, GuideXf, SeenXf> xg;
+    if constexpr (GUIDED) {
+      xg = GuideXf{xf, allow, gs < 0 ? 0 : gs < a.g_A ? 1 : 2};
+      if (xg.mode == 1) {   // uniform over the workgroup: one row, one state
+        const int* arow = a.g_allow + (int64_t)gs * a.words + (j0 >> 5);
+        const int nw = min((j1 - j0 + 31) >> 5, SAMPLE_STAGE_WORDS);
+        for (int t = threadIdx.x; t < nw; t += 256) allow[t] = arow[t];
+        __syncthreads();
+      }
+    } else {
+      xg = xf;
+    }
     if constexpr (MODE == SAMPLE_PARTIAL) {
       TopkStore store{cv, ci, ((int64_t)row * gridDim.y + blockIdx.y) * SAMPLE_K, 0};
-      topk_block<SAMPLE_K>(a.logits, a.ld, a.V, k, 1.f, nullptr, nullptr, nullptr, 1, chunk, pml, false, xf, store);
+      topk_block<SAMPLE_K>(a.logits, a.ld, a.V, k, 1.f, nullptr, nullptr, nullptr, 1, chunk, pml, false, xg, store);
       for (int t = k + threadIdx.x; t < SAMPLE_K; t += 256) {   // the merge reads 64 per chunk
         cv[store.obase + t] = -INFINITY;
         ci[store.obase + t] = -1;
@@ -130,12 +182,18 @@ sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__
       return;
     } else {
       lse0 = topk_block<SAMPLE_K>(a.logits, a.ld, a.V, k, 1.f, a.out_lse, nullptr, nullptr, 1, chunk, nullptr,
-                                  true, xf, lanes);
+                                  true, xg, lanes);
     }
   }
   if (threadIdx.x >= 64) return;
   const int lane = threadIdx.x;
   const float lse = __shfl(lse0, 0, 64);
+  // Fewer than 64 finite candidates (a guided row that allows m < 64 tokens): lanes m .. 63 hold
+  // v = -inf, so p = exp(-inf - lse) = 0 and c_j = c_{m-1} = ctot for every j >= m.  thr <= ctot in
+  // both branches below, so no c_j of the tail is < thr, nor is c_{m-1}: n <= m, and the pick
+  // js <= n - 1 is a finite candidate.  The -inf tail has probability 0 and is never picked.
+  // m = 0 (nothing allowed, lse = -inf): p is NaN, every comparison is false, n = 1, js = 0 and
+  // lane 0 holds id -1: tok = -1, as for a row without a finite logit.
   const double p = exp((double)lanes.v - (double)lse);
   double c = 0.0;   // c_lane = ((p_0 + p_1) + p_2) + ... : numpy's cumsum
   for (int i = 0; i < SAMPLE_K; ++i) {
@@ -156,6 +214,20 @@ sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__
       if (slot >= 0 && in_id >= 0) {     // a slot belongs to one row: plain read-modify-write
         int* w = a.seen + (int64_t)slot * a.words + (in_id >> 5);
         *w = *w | (int)(1u << (in_id & 31));
+      }
+    }
+    if constexpr (GUIDED) {
+      // the slot belongs to this sequence: plain loads and a plain store.  An EOS or zero-length
+      // token has no bytes and leaves the state; so does tok = -1.  The drawn token's bit was set, so
+      // the walk stays alive; a walk that does not (a token outside every table) keeps the state too.
+      if (gslot >= 0) {
+        int ns = gs < a.g_A ? gs : -1;
+        if (ns >= 0 && t >= 0 && t < a.V) {
+          for (int q = a.tok_off[t], q1 = a.tok_off[t + 1]; q < q1 && ns >= 0 && ns < a.g_A; ++q)
+            ns = a.g_dfa[(int64_t)ns * 256 + a.tok_dat[q]];
+          if (ns < 0 || ns >= a.g_A) ns = gs;
+        }
+        if (ns >= 0) a.g_state[gslot] = ns;
       }
     }
   }
@@ -189,30 +261,37 @@ int64_t sample_ws_floats(int B, int V) {
 }
 
 // the draw of R rows (the decode form: R = a.B; the verify form: R = a.B * a.T)
-template <bool VERIFY>
+template <bool VERIFY, bool GUIDED = false>
 static hipError_t launch_rows(const SampleArgs& a, int R, float* ws, hipStream_t stream) {
   const int nch = topk_chunks(a.V);
   if (nch == 1) {
     if (a.words > SAMPLE_STAGE_WORDS) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((sample_rows_kernel<SAMPLE_SINGLE, VERIFY>), dim3(R, 1), dim3(256), 0, stream, a, nullptr,
-                       nullptr, nullptr, 1);
+    hipLaunchKernelGGL((sample_rows_kernel<SAMPLE_SINGLE, VERIFY, GUIDED>), dim3(R, 1), dim3(256), 0, stream, a,
+                       nullptr, nullptr, nullptr, 1);
     return hipGetLastError();
   }
   if (ws == nullptr) return hipErrorInvalidValue;
   float* cv = ws;
   int* ci = reinterpret_cast<int*>(ws + (int64_t)R * nch * SAMPLE_K);
   float* pml = ws + (int64_t)R * nch * SAMPLE_K * 2;
-  hipLaunchKernelGGL((sample_rows_kernel<SAMPLE_PARTIAL, VERIFY>), dim3(R, nch), dim3(256), 0, stream, a, cv, ci, pml,
-                     nch);
+  hipLaunchKernelGGL((sample_rows_kernel<SAMPLE_PARTIAL, VERIFY, GUIDED>), dim3(R, nch), dim3(256), 0, stream, a, cv,
+                     ci, pml, nch);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((sample_rows_kernel<SAMPLE_MERGE, VERIFY>), dim3(R, 1), dim3(256), 0, stream, a, cv, ci, pml, nch);
+  hipLaunchKernelGGL((sample_rows_kernel<SAMPLE_MERGE, VERIFY, GUIDED>), dim3(R, 1), dim3(256), 0, stream, a, cv, ci,
+                     pml, nch);
   return hipGetLastError();
 }
 
 hipError_t sample_rows(const SampleArgs& a, float* ws, hipStream_t stream) {
   if (a.B == 0) return hipSuccess;
   if (a.V < SAMPLE_K || a.words != (a.V + 31) / 32) return hipErrorInvalidValue;
+  if (a.g_slot != nullptr) {   // the guided form: every guide argument, and the decode form only
+    if (a.T != 0 || a.g_allow == nullptr || a.g_dfa == nullptr || a.tok_off == nullptr || a.tok_dat == nullptr ||
+        a.g_in == nullptr || a.g_state == nullptr || a.g_A < 1 || a.g_S < 1)
+      return hipErrorInvalidValue;
+    return launch_rows<false, true>(a, a.B, ws, stream);
+  }
   if (a.T == 0) return launch_rows<false>(a, a.B, ws, stream);
   if (a.T < 1 || a.T > SAMPLE_VERIFY_MAX_T || a.B > 64 || a.n_rows == nullptr || a.n_acc == nullptr)
     return hipErrorInvalidValue;

@@ -15,7 +15,10 @@ namespace lumen {
 
 constexpr int TOPK_CHUNK = 4096;
 
+// kSkipNegInf: the transform masks columns to -inf and the scan passes over those (the online
+// sum-exp of a list that STARTS with -inf would be exp(-inf - -inf) = NaN); other transforms scan as before
 struct TopkIdentity {
+  static constexpr bool kSkipNegInf = false;
   __device__ __forceinline__ float operator()(const float x, const int) const { return x; }
 };
 
@@ -50,6 +53,9 @@ __device__ __forceinline__ float topk_block(const float* __restrict__ scores, in
   for (int i = 0; i < K; ++i) { v[i] = -INFINITY; id[i] = -1; }
   float m = -INFINITY, l = 0.f;
   auto take = [&](const float x, const int j) {
+    if constexpr (XF::kSkipNegInf) {
+      if (x == -INFINITY) return;   // never a candidate, adds nothing to the sum
+    }
     if (!in_ml) {
       const float xs = x * scale;
       if (xs > m) { l = l * __expf(m - xs) + 1.f; m = xs; }

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional, Sequence
+from typing import Any, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -327,8 +327,53 @@ def seen_words(V: int) -> int:
     return -(-V // 32)
 
 
+class GuideTensors(NamedTuple):
+    """The guided form's tensors of :func:`sample_rows` (on the logits' device).  ``allow`` int32
+    [A, ceil(V / 32)] and ``dfa`` int16 [A, 256] are the arena of grammar states of all resident
+    guides (``dfa`` holds arena-global state ids, -1 = dead); ``tok_off`` int32 [V + 1] and
+    ``tok_dat`` uint8 the CSR of the token bytes; ``slot`` int32 [B] the row of ``state`` a
+    sequence owns (-1: an unguided row), ``g_in`` int32 [B] the state the host feeds (-1: read
+    ``state[slot]``) and ``state`` int32 [S] the states kept on the device, written by the call."""
+    allow: torch.Tensor
+    dfa: torch.Tensor
+    tok_off: torch.Tensor
+    tok_dat: torch.Tensor
+    slot: Any
+    g_in: Any
+    state: torch.Tensor
+
+
+MASK_FILL_DEVICE = -1e30     # see mask_logits_
+
+
+def mask_logits_(logits: torch.Tensor, allow_rows, v0: int = 0, fill: Optional[float] = None) -> torch.Tensor:
+    """The host sampling path's grammar mask: ``allow_rows[b]`` is the allowed-token bitmap of row
+    b's grammar state (int32 words over the whole vocabulary, bit t of word t // 32 = token t; None:
+    an unguided row) and column j of ``logits`` is token ``v0 + j``.  A logit whose bit is clear is
+    set to ``fill``: -inf on the CPU.  On the GPU the default is -1e30, because row_topk's online
+    sum-exp must not meet -inf before a finite value; exp(-1e30 - max) is exactly 0, so the
+    log-sum-exp, the finite candidates and the draw are those of the -inf form bit for bit."""
+    rows = [b for b, a in enumerate(allow_rows) if a is not None]
+    if not rows:
+        return logits
+    if fill is None:
+        fill = MASK_FILL_DEVICE if logits.is_cuda else float("-inf")
+    d = logits.device
+    need = seen_words(v0 + logits.shape[1])       # a row shorter than the vocabulary allows nothing beyond it
+    w = torch.zeros((len(rows), max(need, max(len(allow_rows[b]) for b in rows))), dtype=torch.int32)
+    for k, b in enumerate(rows):
+        w[k, :len(allow_rows[b])] = torch.as_tensor(np.asarray(allow_rows[b]), dtype=torch.int32)
+    w = w.to(d)
+    cols = torch.arange(v0, v0 + logits.shape[1], device=d)
+    ok = ((w[:, cols >> 5] >> (cols & 31)) & 1).bool()
+    idx = torch.as_tensor(rows, device=d)
+    logits[idx] = logits[idx].masked_fill(~ok, fill)
+    return logits
+
+
 def sample_rows(logits: torch.Tensor, inv_t, top_p, penalty, u, greedy, seen_slot, seen: torch.Tensor, in_ids,
-                out_ids: Optional[torch.Tensor] = None, candidates: bool = True):
+                out_ids: Optional[torch.Tensor] = None, candidates: bool = True, *,
+                guide: Optional[GuideTensors] = None):
     """Penalise, scale, cut and draw one token per row of fp32 ``logits`` [B, V] without writing them:
     what :func:`rep_penalty_`, the 1/T multiply, ``row_topk(64)`` and :func:`sample_from_candidates`
     do in turn on the host path.
@@ -341,7 +386,14 @@ def sample_rows(logits: torch.Tensor, inv_t, top_p, penalty, u, greedy, seen_slo
 
     Returns ``(v [B, 64], i [B, 64], lse [B], tok [B] int32, seen)``; ``v`` are the transformed
     logits of the candidates, descending.  ``candidates=False`` on the GPU: ``v, i, lse`` are None.
-    CPU tensors run an fp32 / fp64 reference of the same operations."""
+    CPU tensors run an fp32 / fp64 reference of the same operations.
+
+    ``guide`` (:class:`GuideTensors`): the guided form.  A row with ``slot >= 0`` has the grammar
+    state ``s = g_in[b]`` if that is >= 0, else ``state[slot[b]]``; the logits of the tokens whose bit
+    in ``allow[s]`` is clear count as -inf before the penalty, the drawn token's bytes are walked
+    through ``dfa`` from ``s`` and the result is stored in ``state[slot[b]]`` (a token without bytes
+    leaves it).  A row that allows no finite logit gives ``tok = -1`` and keeps its state.  The
+    result gains a sixth element, ``state``."""
     d = logits.device
     B, V = logits.shape
     as_t = lambda x, dt: torch.as_tensor(x, dtype=dt, device=d).reshape(B).contiguous()  # noqa: E731
@@ -356,6 +408,11 @@ def sample_rows(logits: torch.Tensor, inv_t, top_p, penalty, u, greedy, seen_slo
         v = torch.empty((B, SAMPLE_K), dtype=torch.float32, device=d) if candidates else None
         i = torch.empty((B, SAMPLE_K), dtype=torch.int32, device=d) if candidates else None
         lse = torch.empty(B, dtype=torch.float32, device=d) if candidates else None
+        if guide is not None:
+            hip_ops().sample_rows(logits, inv_t, top_p, penalty, u, greedy, seen_slot, seen, in_ids, out_ids, tok,
+                                  v, i, lse, guide.allow, guide.dfa, guide.tok_off, guide.tok_dat,
+                                  as_t(guide.slot, torch.int32), as_t(guide.g_in, torch.int32), guide.state)
+            return v, i, lse, tok, seen, guide.state
         hip_ops().sample_rows(logits, inv_t, top_p, penalty, u, greedy, seen_slot, seen, in_ids, out_ids, tok,
                               v, i, lse)
         return v, i, lse, tok, seen
@@ -364,6 +421,21 @@ def sample_rows(logits: torch.Tensor, inv_t, top_p, penalty, u, greedy, seen_slo
     x = logits.float().clone()
     feed = in_ids.tolist()
     shifts = torch.arange(32)
+    gstate = [-1] * B        # guided rows: the grammar state the row draws in
+    if guide is not None:
+        gslot, gin = as_t(guide.slot, torch.int32).tolist(), as_t(guide.g_in, torch.int32).tolist()
+        A, S = guide.allow.shape[0], guide.state.numel()
+        for b in range(B):
+            if not 0 <= gslot[b] < S:
+                gslot[b] = -1
+                continue
+            s = gin[b] if gin[b] >= 0 else int(guide.state[gslot[b]])
+            gstate[b] = s if 0 <= s < A else A
+            if gstate[b] == A:
+                x[b] = float("-inf")
+            else:
+                ok = ((guide.allow[s].long()[:, None] >> shifts) & 1).bool().reshape(-1)[:V]
+                x[b, ~ok] = float("-inf")
     for b in range(B):
         slot = int(seen_slot[b])
         if slot < 0 or slot >= seen.shape[0] or float(penalty[b]) == 1.0:
@@ -381,19 +453,37 @@ def sample_rows(logits: torch.Tensor, inv_t, top_p, penalty, u, greedy, seen_slo
     vn, lsen = v.numpy(), lse.numpy()
     for b in range(B):
         j = 0
-        if not int(greedy[b]):
+        if guide is not None and vn[b, 0] == -np.inf:      # nothing allowed (or nothing finite): no draw
+            pass
+        elif not int(greedy[b]):
             tp = float(top_p[b])
             c = np.cumsum(np.exp(vn[b].astype(np.float64) - np.float64(lsen[b])))
             n = int(np.searchsorted(c, tp * c[-1] if c[-1] < tp else tp) + 1)
             n = max(1, min(n, SAMPLE_K))
             j = min(n - 1, int(np.searchsorted(c[:n] / c[n - 1], float(u[b]), side="right")))
-        tok[b] = i[b, j]
+        tok[b] = -1 if guide is not None and vn[b, 0] == -np.inf else i[b, j]
         slot = int(seen_slot[b])
         if 0 <= slot < seen.shape[0] and 0 <= feed[b] < V:
             bit = 1 << (feed[b] & 31)
             seen[slot, feed[b] >> 5] |= bit - (1 << 32) if bit >> 31 else bit
-    out_ids.copy_(tok.long())
-    return v, i.to(torch.int32), lse, tok, seen
+    if guide is None:
+        out_ids.copy_(tok.long())
+        return v, i.to(torch.int32), lse, tok, seen
+    off, dat = guide.tok_off.tolist(), guide.tok_dat.tolist()
+    for b in range(B):
+        s, t = gstate[b], int(tok[b])
+        if gslot[b] < 0 or s >= A:
+            continue
+        ns = s
+        if 0 <= t < V:
+            for q in range(off[t], off[t + 1]):
+                ns = int(guide.dfa[ns, dat[q]])
+                if not 0 <= ns < A:
+                    ns = s
+                    break
+        guide.state[gslot[b]] = ns
+    out_ids.copy_(tok.long().clamp(min=0))
+    return v, i.to(torch.int32), lse, tok, seen, guide.state
 
 
 SAMPLE_VERIFY_MAX_T = 8      # rows per sequence of the sampler's verify form (csrc/sampler.h)

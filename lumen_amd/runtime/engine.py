@@ -27,7 +27,16 @@ host<->device every token (packages/lumen-vlm/src/lumen_vlm/backends/onnxrt_back
   leading 64-token blocks carry the content keys of an earlier prompt starts from that prompt's
   KV blocks and prefills only the rest (the chunk path above, ``start_pos`` = the hit); a prompt
   publishes its full blocks to the block manager's index once its prefill succeeded.  Not under
-  tensor parallelism: with ``tp_sync`` the keys are ignored.
+  tensor parallelism: with ``tp_sync`` the keys are ignored;
+* guided decoding (``SamplingParams.guide``, a :class:`~lumen_amd.runtime.guided.Guide`): the request
+  draws only tokens that keep its text a prefix of a match of the guide's grammar, and EOS only
+  when the text is a match.  A batch with a guided request decodes through the ``guided`` graphs:
+  the device sampler masks the logits by the row of the request's grammar state and advances the
+  state itself, so look-ahead stays on; the host keeps the same state for the steps it feeds and
+  for the host sampling path.  Such a request ends with reason ``stop`` at EOS, or ``length`` when
+  ``max_new_tokens`` cuts it -- its text may then be an incomplete match.  Not with speculative
+  decoding (a batch with a guided request takes no verify steps) and not under tensor parallelism
+  (``submit`` raises).
 
 Tensor parallelism: rank 0 runs this loop and broadcasts every step (prefill inputs,
 decode token ids / positions / slots / block tables) to follower ranks running
@@ -69,6 +78,7 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     stop_token_ids: tuple = ()
     seed: Optional[int] = None
+    guide: Any = None                       # runtime.guided.Guide: constrain the output to its grammar
 
 
 @dataclass
@@ -98,6 +108,9 @@ class GenRequest:
     hist: Optional[list] = None             # ... prompt ids + tokens, as the drafter sees them
     hist0: int = 0                          # ... prompt ids in hist
     draft: tuple = (-1, ())                 # ... (len(tokens) it was made for, proposal)
+    gstate: int = -1                        # guided decoding: the grammar state after ``tokens`` (host side)
+    guide_slot: Optional[int] = None        # ... row of the device's state array
+    guide_base: Optional[int] = None        # ... first arena row of the request's guide
 
     def stream(self, timeout: Optional[float] = None) -> Iterator[tuple]:
         """yields ("token", id) ... then ("done", reason) | raises the engine error."""
@@ -136,12 +149,18 @@ class Sampler:
         sample = any(r.params.temperature > 0 for r in reqs)
         pens = [float(r.params.repetition_penalty) for r in reqs]
         use_pen = any(abs(p - 1.0) > 1e-6 for p in pens)
-        return {"k": Sampler.K_SAMPLE if sample else 8,
+        spec = {"k": Sampler.K_SAMPLE if sample else 8,
                 "inv": [1.0 / r.params.temperature if r.params.temperature > 0 else 1.0 for r in reqs] if sample else None,
                 "pen": pens if use_pen else None,
                 "pen_ids": [list(r.tokens) for r in reqs] if use_pen else None}
+        if any(r.params.guide is not None for r in reqs):
+            # guided rows: the allowed-token bitmap of the request's grammar state (host state)
+            spec["allow"] = [r.params.guide.allow[r.gstate] if r.params.guide is not None else None for r in reqs]
+        return spec
 
     def candidates(self, logits: torch.Tensor, spec: dict):
+        if spec.get("allow") is not None:      # before the penalty and the 1/T, as the device sampler masks
+            lops.mask_logits_(logits, spec["allow"], self.llm.v0)
         if spec["pen"] is not None:
             lops.rep_penalty_(logits, [[t - self.llm.v0 for t in ids] for ids in spec["pen_ids"]], spec["pen"])
         if spec["inv"] is not None:
@@ -427,6 +446,92 @@ class SeenSlots:
         seen[slot].copy_(torch.from_numpy(row.view(np.int32)))
 
 
+class GuideArena:
+    """The device side of guided decoding: ``LUMEN_GUIDED_STATES`` rows (default 4096; 19 KB each
+    at V = 151,936) of allowed-token bitmaps and of byte transitions in arena-global state ids, the
+    CSR of the token bytes (one copy per engine) and one grammar state per running sequence.
+
+    Allocated once, before the first ``guided`` graph is captured, so the pointers the graphs hold
+    stay valid.  A guide is uploaded on first use into a free run of rows and stays resident; when
+    a new one does not fit, the least recently used guides that no running request refers to are
+    evicted.  A guide that cannot fit raises :class:`~lumen_amd.runtime.guided.GuideError`, which
+    fails that request only."""
+
+    def __init__(self, llm, max_batch: int, token_bytes: Sequence[bytes], rows: Optional[int] = None):
+        from .guided import token_csr
+
+        d = llm.embed.device
+        self.V = llm.Vl
+        self.rows = int(rows or os.environ.get("LUMEN_GUIDED_STATES", 4096))
+        if not 1 <= self.rows <= 32767:
+            raise ValueError("LUMEN_GUIDED_STATES: 1 .. 32767 (arena-global state ids are int16)")
+        self.words = lops.seen_words(self.V)
+        self.allow = torch.zeros((self.rows, self.words), dtype=torch.int32, device=d)
+        self.dfa = torch.full((self.rows, 256), -1, dtype=torch.int16, device=d)
+        self.token_bytes = token_bytes
+        tb = list(token_bytes[:self.V]) + [b""] * max(0, self.V - len(token_bytes))
+        off, dat = token_csr(tb)
+        self.tok_off = torch.from_numpy(off).to(d)
+        self.tok_dat = torch.from_numpy(dat.copy()).to(d)
+        self.state = torch.zeros(max(max_batch, 1), dtype=torch.int32, device=d)
+        self._free_slots = list(range(max(max_batch, 1) - 1, -1, -1))
+        self._res: "dict[int, dict]" = {}      # id(guide) -> {"g", "base", "n", "refs"}, least recently used first
+
+    def take_slot(self) -> Optional[int]:
+        return self._free_slots.pop() if self._free_slots else None
+
+    def free_slot(self, slot: int) -> None:
+        self._free_slots.append(slot)
+
+    def _gap(self, n: int) -> Optional[int]:
+        """first row of a free run of ``n`` rows (first fit), or None"""
+        at = 0
+        for e in sorted(self._res.values(), key=lambda e: e["base"]):
+            if e["base"] - at >= n:
+                return at
+            at = e["base"] + e["n"]
+        return at if self.rows - at >= n else None
+
+    def acquire(self, g) -> int:
+        """first arena row of guide ``g``, uploading it if it is not resident; takes a reference"""
+        from .guided import GuideError
+
+        e = self._res.pop(id(g), None)
+        if e is None:
+            n = g.n_states
+            if g.token_bytes is not self.token_bytes and list(g.token_bytes) != list(self.token_bytes):
+                raise GuideError("the guide was compiled for another vocabulary than this engine's guides")
+            if n > self.rows or g.V > self.V:
+                raise GuideError(f"a guide of {n} states over {g.V} tokens does not fit the arena "
+                                 f"(LUMEN_GUIDED_STATES = {self.rows}, vocabulary {self.V})")
+            base = self._gap(n)
+            while base is None:
+                idle = next((k for k, v in self._res.items() if v["refs"] == 0), None)
+                if idle is None:
+                    raise GuideError(f"no room for a guide of {n} states: the arena's {self.rows} rows "
+                                     "(LUMEN_GUIDED_STATES) are held by the guides of running requests")
+                del self._res[idle]
+                base = self._gap(n)
+            # on the current stream, the one the graphs replay on: after every step launched before
+            rows = np.zeros((n, self.words), np.int32)
+            rows[:, :g.allow.shape[1]] = g.allow
+            self.allow[base:base + n].copy_(torch.from_numpy(rows))
+            dfa = np.where(g.dfa >= 0, g.dfa.astype(np.int32) + base, -1).astype(np.int16)
+            self.dfa[base:base + n].copy_(torch.from_numpy(dfa))
+            e = {"g": g, "base": base, "n": n, "refs": 0}
+        e["refs"] += 1
+        self._res[id(g)] = e                   # most recently used last
+        return e["base"]
+
+    def release(self, g) -> None:
+        e = self._res.get(id(g))
+        if e is not None and e["refs"] > 0:
+            e["refs"] -= 1
+
+    def tensors(self, g_slot: torch.Tensor, g_in: torch.Tensor):
+        return lops.GuideTensors(self.allow, self.dfa, self.tok_off, self.tok_dat, g_slot, g_in, self.state)
+
+
 class DecodeGraphs(SeenSlots):
     """hipGraph-captured decode steps, one graph per (padded batch-size, table-width) bucket.
 
@@ -470,6 +575,12 @@ class DecodeGraphs(SeenSlots):
     sampler's per-sequence rows (as in ``sample`` mode) and one uniform per row; the result buffer is
     the drawn token of every row, the accepted draft tokens of every sequence and the error word.
     Padded sequences are greedy with slot -1 and one live row.
+
+    ``mode="guided"`` graphs are the ``sample`` graphs with the sampler's guided form: the step
+    buffer also carries per row the sequence's row of the device's grammar states (``g_slot``, -1
+    for an unguided or padded row) and the state the host feeds (``g_in``, -1 on a look-ahead step,
+    which reads the state the step before it stored).  They need :attr:`arena` (a
+    :class:`GuideArena`), set before the first of them is captured.
     """
 
     BUCKETS = (1, 2, 4, 8, 16, 32, 64, 128)
@@ -487,6 +598,7 @@ class DecodeGraphs(SeenSlots):
         self.pool = None
         self.in_graph_sampler = not llm.tp.enabled or os.environ.get("LUMEN_TP_INGRAPH_SAMPLER", "1") == "1"
         self._stream = None     # the capture stream, private to this instance (see _capture_stream)
+        self.arena: Optional[GuideArena] = None      # guided mode: set by the engine before its first capture
 
     def _bucket(self, B: int) -> int:
         for b in self.buckets:
@@ -526,6 +638,19 @@ class DecodeGraphs(SeenSlots):
     _SAMPLE_ROWS = {"u": torch.float64, "top_p": torch.float64, "inv_t": torch.float32, "penalty": torch.float32,
                     "greedy": torch.int32, "seen_slot": torch.int32}
     _SAMPLE_PAD = {"u": 0.0, "top_p": 1.0, "inv_t": 1.0, "penalty": 1.0, "greedy": 1, "seen_slot": -1}
+    _GUIDE_ROWS = {"g_slot": torch.int32, "g_in": torch.int32}      # guided mode, after the sampler's rows
+    _GUIDE_PAD = {"g_slot": -1, "g_in": -1}
+
+    @staticmethod
+    def _layout_guided(Bp: int, W: int) -> dict:
+        """the sample layout followed by (g_slot i32, g_in i32)"""
+        lay = dict(DecodeGraphs._layout_sample(Bp, W))
+        o = lay["bytes"]
+        for k in DecodeGraphs._GUIDE_ROWS:
+            lay[k] = (o, Bp)
+            o += 4 * Bp
+        lay["bytes"] = -(-o // 16) * 16
+        return lay
 
     def _capture_stream(self, d: torch.device) -> torch.cuda.Stream:
         """One stream per engine that nothing else ever uses.  The split-K tickets and
@@ -558,8 +683,11 @@ class DecodeGraphs(SeenSlots):
 
     def _capture(self, Bp: int, W: int, mode: str = "greedy") -> dict:
         d = self.llm.embed.device
-        sample = mode == "sample"
-        lay = self._layout_sample(Bp, W) if sample else self._layout(Bp, W)
+        guided = mode == "guided"
+        sample = mode == "sample" or guided
+        if guided and self.arena is None:
+            raise RuntimeError("guided graphs need the guide arena")
+        lay = self._layout_guided(Bp, W) if guided else self._layout_sample(Bp, W) if sample else self._layout(Bp, W)
         dbuf = torch.zeros(lay["bytes"], dtype=torch.uint8, device=d)
 
         def views(buf):
@@ -574,6 +702,10 @@ class DecodeGraphs(SeenSlots):
                 for k, dt in self._SAMPLE_ROWS.items():
                     o, n = lay[k]
                     v[k] = buf[o:o + dt.itemsize * n].view(dt)
+            if guided:
+                for k, dt in self._GUIDE_ROWS.items():
+                    o, n = lay[k]
+                    v[k] = buf[o:o + dt.itemsize * n].view(dt)
             return v
 
         st = views(dbuf)
@@ -582,6 +714,10 @@ class DecodeGraphs(SeenSlots):
         if sample:
             for k, pad in self._SAMPLE_PAD.items():
                 st[k].fill_(pad)
+        if guided:
+            for k, pad in self._GUIDE_PAD.items():
+                st[k].fill_(pad)
+            ar = self.arena
         if Bp not in self.ids:
             self.ids[Bp] = torch.zeros(Bp, dtype=torch.long, device=d)
         ids = self.ids[Bp]
@@ -599,7 +735,14 @@ class DecodeGraphs(SeenSlots):
 
         def run():
             logits = self.llm.decode(ids, st["pos"], st["slots"], self.kv, st["bt"], st["ctx"], workspace=ws)
-            if sample:
+            if guided:
+                # the sample call below with the guided form's tensors: masks by the row's grammar state
+                # (st["g_in"], or the arena's state array on a look-ahead step) and stores the new state
+                ops.hip_ops().sample_rows(logits, st["inv_t"], st["top_p"], st["penalty"], st["u"], st["greedy"],
+                                          st["seen_slot"], seen, ids, ids, res[:Bp], None, None, None,
+                                          ar.allow, ar.dfa, ar.tok_off, ar.tok_dat, st["g_slot"], st["g_in"],
+                                          ar.state)
+            elif sample:
                 # reads ids (the step's input tokens: penalised and marked) and writes the drawn ones back
                 ops.hip_ops().sample_rows(logits, st["inv_t"], st["top_p"], st["penalty"], st["u"], st["greedy"],
                                           st["seen_slot"], seen, ids, ids, res[:Bp], None, None, None)
@@ -651,9 +794,11 @@ class DecodeGraphs(SeenSlots):
         replay of this batch bucket wrote on the device).  Returns a handle for
         :meth:`tokens` / :meth:`logits`.  ``fetch=False`` (TP followers): no result copy.
         ``sample``: per-row arrays of the device sampler (keys of ``_SAMPLE_ROWS``) -- the step
-        runs the ``sample`` graph and :meth:`sampled` reads its tokens."""
+        runs the ``sample`` graph and :meth:`sampled` reads its tokens; with the keys of
+        ``_GUIDE_ROWS`` too, the ``guided`` graph."""
         B = len(pos)
-        e = self._entry(B, bt.shape[1], "greedy" if sample is None else "sample")
+        guided = sample is not None and "g_slot" in sample
+        e = self._entry(B, bt.shape[1], "greedy" if sample is None else "guided" if guided else "sample")
         Bp, W = e["Bp"], e["W"]
         par = e["par"]
         e["par"] ^= 1
@@ -675,6 +820,11 @@ class DecodeGraphs(SeenSlots):
                 a = hv[k].numpy()
                 a[:] = pad
                 a[:B] = sample[k]
+            if guided:
+                for k, pad in self._GUIDE_PAD.items():
+                    a = hv[k].numpy()
+                    a[:] = pad
+                    a[:B] = sample[k]
         e["dbuf"].copy_(e["h_step"][par], non_blocking=True)
         if ids is not None:
             hi = e["h_ids"][par].numpy()
@@ -899,7 +1049,9 @@ class LLMEngine:
         self.device = llm.embed.device
         self.stats = {"prefills": 0, "prefill_chunks": 0, "decode_steps": 0, "tokens": 0,
                       "prefix_hits": 0, "prefix_tokens": 0, "prefill_tokens": 0,
-                      "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0, "spec_sample_steps": 0}
+                      "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0, "spec_sample_steps": 0,
+                      "guided_steps": 0}
+        self._arena: Optional[GuideArena] = None     # guided decoding's device tables, built on first need
         if use_graphs is None:
             use_graphs = os.environ.get("LUMEN_HIP_GRAPHS", "1") == "1"
         self.graphs: Optional[DecodeGraphs] = None
@@ -967,6 +1119,11 @@ class LLMEngine:
             need = prompt_len + params.max_new_tokens
             if need > self.kv.capacity_tokens:
                 raise ValueError(f"request needs {need} KV tokens, cache holds {self.kv.capacity_tokens}")
+            if params.guide is not None:
+                if self.sync is not None or self.llm.tp.enabled:
+                    raise ValueError("guided decoding is not supported under tensor parallelism")
+                if params.guide.V > self.llm.Vl:
+                    raise ValueError(f"the guide covers {params.guide.V} tokens, the model's vocabulary {self.llm.Vl}")
         except Exception:
             self.release_prefix(hit)
             raise
@@ -985,6 +1142,8 @@ class LLMEngine:
         r = GenRequest(rid=hit.rid, prefill_args=prefill_args, prompt_len=prompt_len, params=params,
                        t_submit=time.perf_counter(), rng=np.random.default_rng(params.seed),
                        cached_tokens=hit.tokens, prefix_keys=keys, prompt_ids=prompt_ids)
+        if params.guide is not None:
+            r.gstate = params.guide.start
         self._waiting.put(r)
         return r
 
@@ -1002,6 +1161,14 @@ class LLMEngine:
     def _emit(self, r: GenRequest, tok: int) -> bool:
         """record token; returns True when the request finished."""
         p = r.params
+        if p.guide is not None:
+            # the host's copy of the grammar state: what a fed step and the host sampling path mask by
+            if not p.guide.allows(r.gstate, tok):
+                raise RuntimeError(f"guided decoding: token {tok} is not allowed in grammar state {r.gstate}")
+            if tok in p.stop_token_ids or tok in p.guide.eos_ids:     # EOS: only allowed in an accepting state
+                r.finish_reason = "stop"
+                return True
+            r.gstate = p.guide.walk(r.gstate, tok)
         if tok in p.stop_token_ids:
             r.finish_reason = "eos_token"
             return True
@@ -1029,10 +1196,29 @@ class LLMEngine:
                 r.seen_n = len(r.tokens) - 1
         self._running.append(r)
 
+    def _guide_acquire(self, r: GenRequest) -> None:
+        """a guided request that may decode through the ``guided`` graphs takes its guide's arena
+        rows (uploading the guide on first use) and a row of the device's grammar states.  A guide
+        that does not fit raises GuideError: the caller fails this request only."""
+        g = r.params.guide
+        if g is None or r.guide_base is not None or self.graphs is None or not self.ingraph_sampling \
+                or not _LOOKAHEAD:
+            return
+        if self._arena is None:
+            self._arena = GuideArena(self.llm, self.max_batch, g.token_bytes)
+        self.graphs.arena = self._arena
+        r.guide_base = self._arena.acquire(g)
+        r.guide_slot = self._arena.take_slot()
+
     def _drop_slot(self, r: GenRequest) -> None:
         if r.seen_slot is not None and self._slots is not None:
             self._slots.free_slot(r.seen_slot)
         r.seen_slot = None
+        if r.guide_base is not None and self._arena is not None:
+            self._arena.release(r.params.guide)
+            if r.guide_slot is not None:
+                self._arena.free_slot(r.guide_slot)
+        r.guide_base = r.guide_slot = None
 
     def _finish(self, r: GenRequest) -> None:
         self._drop_slot(r)
@@ -1073,6 +1259,7 @@ class LLMEngine:
         if r.x is None:
             if r.t_admit is None:
                 r.t_admit = time.perf_counter()
+            self._guide_acquire(r)
             if self.sync is not None:
                 # followers must enter the build (its vocab-parallel embedding all-reduce)
                 # together with us: announce it before building the inputs
@@ -1147,7 +1334,14 @@ class LLMEngine:
         g = self.graphs
         return (g is not None and g.in_graph_sampler and _LOOKAHEAD
                 and spec["inv"] is None and spec["pen"] is None and spec["k"] <= g.K_GREEDY
-                and len(reqs) <= g.buckets[-1])
+                and spec.get("allow") is None and len(reqs) <= g.buckets[-1])
+
+    def _guided_graph_ok(self, reqs, spec) -> bool:
+        """the ``guided`` graphs serve this step: what the device sampler needs, and every guided
+        request holds its guide's arena rows and a row of the device's grammar states"""
+        return (self._sample_graph_ok(reqs, spec) and self._arena is not None
+                and all(r.guide_base is not None and r.guide_slot is not None
+                        for r in reqs if r.params.guide is not None))
 
     def _sample_graph_ok(self, reqs, spec) -> bool:
         """the in-graph device sampler serves this step: single GPU, graphs and look-ahead on, at
@@ -1174,9 +1368,10 @@ class LLMEngine:
             del r.us[k]
         return r.us[n]
 
-    def _sample_inputs(self, reqs, ahead: int, fed: bool) -> dict:
+    def _sample_inputs(self, reqs, ahead: int, fed: bool, guided: bool = False) -> dict:
         """per-row inputs of the device sampler for the step that yields token len(tokens) + ahead;
-        ``fed``: the step gets its input tokens from the host (not a look-ahead)"""
+        ``fed``: the step gets its input tokens from the host (not a look-ahead); ``guided``: the
+        step runs the ``guided`` graph and also carries the rows' grammar-state slots and states"""
         for r in reqs:
             if r.seen_slot is None:
                 continue
@@ -1188,13 +1383,21 @@ class LLMEngine:
             else:
                 r.seen_n = n + 1                  # ... and this one the token the step before it draws
         ps = [r.params for r in reqs]
-        return {"inv_t": np.array([1.0 / p.temperature if p.temperature > 0 else 1.0 for p in ps], np.float32),
-                "top_p": np.array([p.top_p for p in ps], np.float64),
-                "penalty": np.array([float(p.repetition_penalty) if r.seen_slot is not None else 1.0
-                                     for p, r in zip(ps, reqs)], np.float32),
-                "greedy": np.array([p.temperature <= 0 for p in ps], np.int32),
-                "seen_slot": np.array([-1 if r.seen_slot is None else r.seen_slot for r in reqs], np.int32),
-                "u": np.array([self._uniform(r, len(r.tokens) + ahead) for r in reqs], np.float64)}
+        out = {"inv_t": np.array([1.0 / p.temperature if p.temperature > 0 else 1.0 for p in ps], np.float32),
+               "top_p": np.array([p.top_p for p in ps], np.float64),
+               "penalty": np.array([float(p.repetition_penalty) if r.seen_slot is not None else 1.0
+                                    for p, r in zip(ps, reqs)], np.float32),
+               "greedy": np.array([p.temperature <= 0 for p in ps], np.int32),
+               "seen_slot": np.array([-1 if r.seen_slot is None else r.seen_slot for r in reqs], np.int32),
+               "u": np.array([self._uniform(r, len(r.tokens) + ahead) for r in reqs], np.float64)}
+        if guided:
+            # a fed step carries the state the host derived from the request's tokens; a look-ahead
+            # step reads the one the step before it stored, so a discarded look-ahead step that is
+            # launched again as a fed step cannot advance the state twice
+            gd = [r.params.guide is not None for r in reqs]
+            out["g_slot"] = np.array([r.guide_slot if g else -1 for r, g in zip(reqs, gd)], np.int32)
+            out["g_in"] = np.array([r.guide_base + r.gstate if g and fed else -1 for r, g in zip(reqs, gd)], np.int32)
+        return out
 
     def _graph_ready(self, reqs, mode: str = "greedy") -> bool:
         """the step's graph exists or captures now (a capture failure disables graphs).  Under
@@ -1241,6 +1444,8 @@ class LLMEngine:
         sampler's 64 candidates and every penalised request holds a bitmap slot"""
         if not (self.drafter is not None and self.sync is None and not self.llm.tp.enabled
                 and len(reqs) * self.spec_T <= 32):
+            return False
+        if any(r.params.guide is not None for r in reqs):      # guided requests take no verify steps
             return False
         if not self._spec_sampled(reqs):
             return True
@@ -1395,31 +1600,36 @@ class LLMEngine:
                 self._verify(reqs, drafts)
                 return
         spec = Sampler.spec(reqs)
-        mode = "greedy" if self._greedy_graph_ok(reqs, spec) else "sample" if self._sample_graph_ok(reqs, spec) \
-            else None
+        if spec.get("allow") is not None:      # a batch with a guided request: the guided graphs or the host path
+            mode = "guided" if self._guided_graph_ok(reqs, spec) else None
+        else:
+            mode = "greedy" if self._greedy_graph_ok(reqs, spec) else "sample" if self._sample_graph_ok(reqs, spec) \
+                else None
         if mode is not None and self._graph_ready(reqs, mode):
             # look-ahead decode: the step after this one is launched (token ids taken from this
             # step's in-graph arg-max or draw) BEFORE this step's tokens are read, so the host work of
             # reading, streaming and scheduling overlaps the GPU instead of idling it between steps
             rids = [r.rid for r in reqs]
-            smp = mode == "sample"       # the mode follows from the requests, so a pending step has the same
+            gd = mode == "guided"
+            smp = mode == "sample" or gd      # the mode follows from the requests, so a pending step has the same
             pend, self._pending = self._pending, None
             if pend is not None and pend[0] == rids:
                 h = pend[1]
             else:
                 ids = np.array([r.tokens[-1] for r in reqs], np.int64)
                 h = self._launch_greedy(ids, self._step_inputs(reqs, 0), spec,
-                                        self._sample_inputs(reqs, 0, True) if smp else None)
+                                        self._sample_inputs(reqs, 0, True, gd) if smp else None)
             nxt = None
             # with a drafter the next step may be a verify step, known only once this step's tokens
             # are read: the look-ahead is then launched after them, and only if nothing was drafted
             late = self._spec_ok(reqs)
             if not late and self._can_look_ahead(reqs):
                 nxt = self._launch_greedy(None, self._step_inputs(reqs, 1), spec,
-                                          self._sample_inputs(reqs, 1, False) if smp else None)
+                                          self._sample_inputs(reqs, 1, False, gd) if smp else None)
             if smp:
                 toks = [int(t) for t in self.graphs.sampled(h)]
-                self.stats["ingraph_sample_steps"] = self.stats.get("ingraph_sample_steps", 0) + 1
+                self.stats["guided_steps" if gd else "ingraph_sample_steps"] = \
+                    self.stats.get("guided_steps" if gd else "ingraph_sample_steps", 0) + 1
             else:
                 _v, i, _lse = self.graphs.tokens(h)
                 toks = [int(i[b, 0]) for b in range(B)]
@@ -1439,7 +1649,7 @@ class LLMEngine:
             if late and len(still) == B and self._can_look_ahead(reqs) and self._spec_drafts(reqs) is None:
                 nxt = self._launch_greedy(np.array([r.tokens[-1] for r in reqs], np.int64),
                                           self._step_inputs(reqs, 0), spec,      # ctx already advanced
-                                          self._sample_inputs(reqs, 0, True) if smp else None)
+                                          self._sample_inputs(reqs, 0, True, gd) if smp else None)
             if nxt is not None and len(still) == B:
                 self._pending = (rids, nxt)
                 self.stats["lookahead_steps"] = self.stats.get("lookahead_steps", 0) + 1

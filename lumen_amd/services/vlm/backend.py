@@ -641,12 +641,29 @@ class MI355XVLMBackend:
         stops.update(int(t) for t in extra_eos)
         sp = SamplingParams(max_new_tokens=max(1, int(req.max_new_tokens)), temperature=float(req.temperature),
                             top_p=float(req.top_p), repetition_penalty=float(req.repetition_penalty),
-                            stop_token_ids=tuple(stops), seed=req.extra.get("seed"))
+                            stop_token_ids=tuple(stops), seed=req.extra.get("seed"),
+                            guide=self._guide(req.extra.get("guided"), stops))
         r = self.engine.submit((ids, img if starts else None), len(full), sp, prefix_keys=keys, hit=hit,
                                prompt_ids=full)
         if hit is not None:
             hit.tokens = 0      # the request owns the references now
         return r
+
+    def _guide(self, guided, stops):
+        """the compiled guide of a request's (kind, spec text), from the cache of compiled guides or
+        compiled here, in the request's thread; the stop token ids are its end-of-sequence ids"""
+        if not guided:
+            return None
+        from ...runtime import guided as gd
+
+        if self.tp.enabled or self._tp_group is not None:
+            raise InvalidInputError("guided decoding is not supported under tensor parallelism")
+        kind, spec = guided
+        try:
+            tok = self.tokenizer()
+            return gd.cached_guide(kind, spec, gd.token_bytes_of(tok), sorted(stops), vocab_key=id(tok))
+        except gd.GuideError as e:
+            raise InvalidInputError(f"guided_{'json' if kind == 'json_schema' else kind}: {e}") from e
 
     def _remote_result(self, request: GenerationRequest) -> GenerationResult:
         """One generation on the engine, completed on its own (not with a merged batch)."""

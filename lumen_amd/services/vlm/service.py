@@ -6,7 +6,9 @@ non-empty content; image <= 50 MB) and fastvlm_service.py:47-591: tasks
 ``vlm_generate`` / ``vlm_generate_stream`` (image MIME payload, limits
 ``max_image_size`` 5048x5048), meta ``messages`` (JSON list) or ``prompt``,
 ``max_new_tokens`` 512, ``temperature`` 0, ``top_p`` 1, ``repetition_penalty`` 1,
-``do_sample``, ``add_generation_prompt`` true, ``stop_sequences`` (JSON list); response
+``do_sample``, ``add_generation_prompt`` true, ``stop_sequences`` (JSON list), at most one of
+``guided_choice`` (JSON list of strings) / ``guided_regex`` / ``guided_json`` (a JSON schema as
+text; runtime/guided.py, response meta ``guided`` = the kind); response
 meta ``generated_tokens``, ``finish_reason`` (+ ``streaming_chunks``) and
 ``processing_time_ms``; ``SERVICE_NAME`` "vlm-fast".
 
@@ -212,7 +214,31 @@ class GeneralFastVLMService(BaseInferenceService):
                  stop_sequences=stops)
         if "seed" in meta:
             p["extra"] = {"seed": _i(meta, "seed", 0)}
+        guided = self._guided(meta)
+        if guided is not None:
+            p.setdefault("extra", {})["guided"] = guided
         return p
+
+    GUIDED_KEYS = {"guided_choice": "choice", "guided_regex": "regex", "guided_json": "json_schema"}
+
+    @classmethod
+    def _guided(cls, meta: dict) -> Optional[tuple]:
+        """(kind, spec text) of the request's guide: at most one of ``guided_choice`` (a JSON list of
+        strings), ``guided_regex`` and ``guided_json`` (a JSON schema as text).  The grammar is checked
+        here, before the image is touched; it is compiled against the vocabulary at submit."""
+        from ...runtime import guided as gd
+
+        keys = [k for k in cls.GUIDED_KEYS if k in meta]
+        if not keys:
+            return None
+        if len(keys) > 1:
+            raise InvalidInputError(f"At most one of {sorted(cls.GUIDED_KEYS)} may be given, got {sorted(keys)}")
+        kind, text = cls.GUIDED_KEYS[keys[0]], str(meta[keys[0]])
+        try:
+            gd.check(kind, text)
+        except gd.GuideError as e:
+            raise InvalidInputError(f"{keys[0]}: {e}") from e
+        return kind, text
 
     def _prep(self, payload: bytes, meta: dict):
         msgs = self._messages(meta)
@@ -240,6 +266,8 @@ class GeneralFastVLMService(BaseInferenceService):
              "cached_tokens": str(int(res.metadata.get("cached_tokens") or 0))}
         if res.metadata.get("ttft_ms") is not None:
             m["ttft_ms"] = f"{res.metadata['ttft_ms']:.2f}"
+        if "guided" in p.get("extra", {}):
+            m["guided"] = p["extra"]["guided"][0]
         return body, rs.MIME_TEXT_GEN, m
 
     def _handle_generate_stream(self, payload: bytes, mime: str, meta: dict):
@@ -257,9 +285,11 @@ class GeneralFastVLMService(BaseInferenceService):
                                               {"temperature": p["temperature"], "top_p": p["top_p"],
                                                "max_tokens": p["max_new_tokens"], "streaming_chunks": n_chunks,
                                                "generation_time_ms": (time.perf_counter() - t0) * 1000})
-                    yield body, rs.MIME_TEXT_GEN, {"generated_tokens": str(n_tok), "finish_reason": reason,
-                                                   "streaming_chunks": str(n_chunks),
-                                                   "cached_tokens": str(int(ch.metadata.get("cached_tokens") or 0))}, True
+                    m = {"generated_tokens": str(n_tok), "finish_reason": reason, "streaming_chunks": str(n_chunks),
+                         "cached_tokens": str(int(ch.metadata.get("cached_tokens") or 0))}
+                    if "guided" in p.get("extra", {}):
+                        m["guided"] = p["extra"]["guided"][0]
+                    yield body, rs.MIME_TEXT_GEN, m, True
                     return
                 n_tok += len(ch.tokens)
                 if ch.text:
@@ -275,5 +305,6 @@ class GeneralFastVLMService(BaseInferenceService):
     def build_capability(self):
         bi = self.backend.get_info()
         extra = {k: str(v) for k, v in bi.as_dict().items() if v is not None and not isinstance(v, list)}
+        extra["guided_decoding"] = json.dumps(["choice", "regex", "json_schema"])
         return self.registry.build_capability(self.SERVICE_NAME, self.resources.model_id, bi.runtime,
                                               list(bi.precisions), extra)
