@@ -443,7 +443,7 @@ __global__ void pool2d_kernel(const uint16_t* __restrict__ x, uint16_t* __restri
     }
   }
   if (!is_max) {
-    const float inv = 1.f / (float)(KH * KW);  // count_include_pad=True (ONNX/PyTorch default)
+    const float inv = 1.f / (float)(KH * KW);  // count_include_pad=True (PyTorch's default; ONNX's is 0)
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] *= inv;
   }

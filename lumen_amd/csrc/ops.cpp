@@ -1049,8 +1049,20 @@ void conv2d_dw(const at::Tensor& x, const at::Tensor& w, const c10::optional<at:
   const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   TORCH_CHECK(C % 8 == 0 && w.size(2) == C, "conv2d_dw: C % 8 / mismatch");
   TORCH_CHECK(out.is_contiguous() && out.dim() == 4 && out.size(3) == C, "conv2d_dw: out");
+  check_gpu(w, "w");
+  check_gpu(out, "out");
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16, "conv2d_dw: w must be bf16");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat, "conv2d_dw: out must be bf16 or f32");
+  TORCH_CHECK(out.size(0) == N, "conv2d_dw: out batch");
+  TORCH_CHECK(stride.size() == 2 && padding.size() == 2 && dilation.size() == 2 && stride[0] > 0 && stride[1] > 0 &&
+                  dilation[0] > 0 && dilation[1] > 0, "conv2d_dw: stride / padding / dilation are (h, w) pairs");
   const void* bp = nullptr; int bf32 = 0;
-  if (bias.has_value() && bias->defined()) { bp = bias->data_ptr(); bf32 = bias->scalar_type() == at::kFloat; }
+  if (bias.has_value() && bias->defined()) {
+    check_gpu(*bias, "bias");
+    TORCH_CHECK(bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16, "conv2d_dw: bias must be f32 or bf16");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == C, "conv2d_dw: bias must hold C contiguous values");
+    bp = bias->data_ptr(); bf32 = bias->scalar_type() == at::kFloat;
+  }
   const at::DeviceGuard guard(x.device());
   LM_CHECK_HIP(lumen::conv2d_depthwise(bf(x), bf(w), bp, bf32, out.data_ptr(), (int)N, (int)H, (int)W, (int)C,
                                           (int)w.size(0), (int)w.size(1), (int)stride[0], (int)stride[1],
@@ -1062,11 +1074,24 @@ void conv2d_dw(const at::Tensor& x, const at::Tensor& w, const c10::optional<at:
 void channel_affine(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift, at::Tensor out,
                     int64_t act, const c10::optional<at::Tensor>& prelu) {
   check_gpu(x, "x");
+  check_gpu(out, "out");
+  check_gpu(scale, "scale");
+  check_gpu(shift, "shift");
   TORCH_CHECK(x.is_contiguous() && out.is_contiguous() && x.scalar_type() == at::kBFloat16, "channel_affine: x/out");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16, "channel_affine: out must be bf16");
+  TORCH_CHECK(out.sizes() == x.sizes(), "channel_affine: out must have the shape of x");
+  TORCH_CHECK(x.dim() >= 1, "channel_affine: x needs a channel dim");
   const int64_t C = x.size(-1);
   TORCH_CHECK(C % 8 == 0 && scale.numel() == C && shift.numel() == C && scale.scalar_type() == at::kFloat, "channel_affine: C");
+  TORCH_CHECK(shift.scalar_type() == at::kFloat, "channel_affine: shift must be f32");
+  TORCH_CHECK(scale.is_contiguous() && shift.is_contiguous(), "channel_affine: scale / shift contiguous");
   const uint16_t* pp = nullptr;
-  if (prelu.has_value() && prelu->defined()) pp = bf(*prelu);
+  if (prelu.has_value() && prelu->defined()) {
+    check_gpu(*prelu, "prelu");
+    TORCH_CHECK(prelu->scalar_type() == at::kBFloat16, "channel_affine: prelu must be bf16");
+    TORCH_CHECK(prelu->is_contiguous() && prelu->numel() == C, "channel_affine: prelu must hold C contiguous slopes");
+    pp = bf(*prelu);
+  }
   const at::DeviceGuard guard(x.device());
   LM_CHECK_HIP(lumen::channel_affine(bf(x), scale.data_ptr<float>(), shift.data_ptr<float>(), bfm(out),
                                         x.numel() / C, (int)C, (int)act, pp, cur_stream()));
@@ -1075,7 +1100,17 @@ void channel_affine(const at::Tensor& x, const at::Tensor& scale, const at::Tens
 void pool2d(const at::Tensor& x, at::Tensor out, std::vector<int64_t> kernel, std::vector<int64_t> stride,
             std::vector<int64_t> padding, bool is_max) {
   check_gpu(x, "x");
+  check_gpu(out, "out");
   TORCH_CHECK(x.is_contiguous() && out.is_contiguous() && x.dim() == 4 && x.size(3) % 8 == 0, "pool2d: NHWC");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "pool2d: x must be bf16");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16, "pool2d: out must be bf16");
+  TORCH_CHECK(kernel.size() == 2 && stride.size() == 2 && padding.size() == 2 && kernel[0] > 0 && kernel[1] > 0 &&
+                  stride[0] > 0 && stride[1] > 0 && padding[0] >= 0 && padding[1] >= 0,
+              "pool2d: kernel / stride / padding are (h, w) pairs");
+  const int64_t Ho = (x.size(1) + 2 * padding[0] - kernel[0]) / stride[0] + 1;
+  const int64_t Wo = (x.size(2) + 2 * padding[1] - kernel[1]) / stride[1] + 1;
+  TORCH_CHECK(out.dim() == 4 && out.size(0) == x.size(0) && out.size(1) == Ho && out.size(2) == Wo &&
+                  out.size(3) == x.size(3), "pool2d: out must be [N, Ho, Wo, C] of the floor-mode pooling");
   const at::DeviceGuard guard(x.device());
   LM_CHECK_HIP(lumen::pool2d(bf(x), bfm(out), (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3),
                                 (int)kernel[0], (int)kernel[1], (int)stride[0], (int)stride[1], (int)padding[0],
@@ -1084,7 +1119,11 @@ void pool2d(const at::Tensor& x, at::Tensor out, std::vector<int64_t> kernel, st
 
 void global_avgpool(const at::Tensor& x, at::Tensor out) {
   check_gpu(x, "x");
+  check_gpu(out, "out");
   TORCH_CHECK(x.is_contiguous() && x.dim() == 4 && out.scalar_type() == at::kFloat, "global_avgpool");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "global_avgpool: x must be bf16");
+  TORCH_CHECK(out.is_contiguous() && out.dim() == 2 && out.size(0) == x.size(0) && out.size(1) == x.size(3),
+              "global_avgpool: out must be contiguous [N, C]");
   const at::DeviceGuard guard(x.device());
   LM_CHECK_HIP(lumen::global_avgpool(bf(x), out.data_ptr<float>(), (int)x.size(0), (int)(x.size(1) * x.size(2)),
                                         (int)x.size(3), cur_stream()));
@@ -1092,10 +1131,21 @@ void global_avgpool(const at::Tensor& x, at::Tensor out) {
 
 void upsample_add(const at::Tensor& x, const c10::optional<at::Tensor>& add, at::Tensor out, int64_t factor) {
   check_gpu(x, "x");
+  check_gpu(out, "out");
   TORCH_CHECK(x.is_contiguous() && x.dim() == 4 && x.size(3) % 8 == 0, "upsample_add: x");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16, "upsample_add: x / out must be bf16");
+  TORCH_CHECK(factor >= 1, "upsample_add: factor");
   const int64_t ldo = pixel_stride(out, "out");
+  TORCH_CHECK(out.size(0) == x.size(0) && out.size(1) == x.size(1) * factor && out.size(2) == x.size(2) * factor &&
+                  out.size(3) == x.size(3), "upsample_add: out must be [N, H*f, W*f, C]");
   const uint16_t* ap = nullptr;
-  if (add.has_value() && add->defined()) { TORCH_CHECK(add->is_contiguous()); ap = bf(*add); }
+  if (add.has_value() && add->defined()) {
+    check_gpu(*add, "add");
+    TORCH_CHECK(add->is_contiguous());
+    TORCH_CHECK(add->scalar_type() == at::kBFloat16 && add->sizes() == out.sizes(),
+                "upsample_add: add must be bf16 of the output shape");
+    ap = bf(*add);
+  }
   const at::DeviceGuard guard(x.device());
   LM_CHECK_HIP(lumen::upsample_add(bf(x), ap, bfm(out), (int)x.size(0), (int)x.size(1), (int)x.size(2),
                                       (int)x.size(3), (int)factor, ldo, cur_stream()));
@@ -1103,7 +1153,11 @@ void upsample_add(const at::Tensor& x, const c10::optional<at::Tensor>& add, at:
 
 void channel_scale_(at::Tensor x, const at::Tensor& s) {
   check_gpu(x, "x");
+  check_gpu(s, "s");
   TORCH_CHECK(x.is_contiguous() && x.dim() == 4 && s.scalar_type() == at::kFloat, "channel_scale_");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "channel_scale_: x must be bf16");
+  TORCH_CHECK(x.size(3) % 8 == 0, "channel_scale_: C % 8 == 0");
+  TORCH_CHECK(s.is_contiguous() && s.numel() == x.size(0) * x.size(3), "channel_scale_: s must be contiguous [N, C]");
   const at::DeviceGuard guard(x.device());
   LM_CHECK_HIP(lumen::channel_scale(bfm(x), s.data_ptr<float>(), (int)x.size(0), (int)(x.size(1) * x.size(2)),
                                        (int)x.size(3), cur_stream()));
@@ -1111,8 +1165,16 @@ void channel_scale_(at::Tensor x, const at::Tensor& s) {
 
 void pixel_shuffle_up(const at::Tensor& y, at::Tensor out, int64_t factor) {
   check_gpu(y, "y");
+  check_gpu(out, "out");
   TORCH_CHECK(y.is_contiguous() && out.is_contiguous(), "pixel_shuffle_up");
+  TORCH_CHECK(y.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16,
+              "pixel_shuffle_up: y / out must be bf16");
+  TORCH_CHECK(y.dim() == 4 && out.dim() == 4 && factor >= 1, "pixel_shuffle_up: NHWC, factor >= 1");
   const int64_t C = out.size(3);
+  TORCH_CHECK(C % 8 == 0, "pixel_shuffle_up: C % 8 == 0");
+  TORCH_CHECK(y.size(3) == factor * factor * C, "pixel_shuffle_up: y must have f*f*C channels");
+  TORCH_CHECK(out.size(0) == y.size(0) && out.size(1) == y.size(1) * factor && out.size(2) == y.size(2) * factor,
+              "pixel_shuffle_up: out must be [N, H*f, W*f, C]");
   const at::DeviceGuard guard(y.device());
   LM_CHECK_HIP(lumen::pixel_shuffle_up(bf(y), bfm(out), (int)y.size(0), (int)y.size(1), (int)y.size(2), (int)C,
                                           (int)factor, cur_stream()));

@@ -50,6 +50,7 @@ bool fp_ok(const at::Tensor& t) { return t.scalar_type() == at::kFloat || t.scal
 void ew_binary(const at::Tensor& a, const at::Tensor& b, at::Tensor out, int64_t op) {
   TORCH_CHECK(a.is_cuda() && b.is_cuda() && out.is_cuda() && fp_ok(a) && fp_ok(b) && fp_ok(out), "ew_binary: dtypes");
   TORCH_CHECK(out.is_contiguous() && out.dim() <= lumen::EW_DIMS, "ew_binary: out contiguous, <= 6 dims");
+  TORCH_CHECK(op >= 0 && op <= 6, "ew_binary: op 0..6");
   const auto ae = a.expand(out.sizes()), be = b.expand(out.sizes());
   lumen::EwArgs p{};
   const int nd = (int)out.dim(), off = lumen::EW_DIMS - nd;
@@ -69,6 +70,7 @@ void ew_binary(const at::Tensor& a, const at::Tensor& b, at::Tensor out, int64_t
 void softmax_rows(const at::Tensor& x, at::Tensor out) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && out.is_contiguous() && fp_ok(x) && fp_ok(out) &&
               x.numel() == out.numel() && x.dim() >= 1, "softmax_rows: contiguous f32/bf16");
+  TORCH_CHECK(out.is_cuda() && out.device() == x.device(), "softmax_rows: out must be on the GPU of x");
   const int64_t D = x.size(-1);
   const at::DeviceGuard g(x.device());
   CHECK_HIP_O(lumen::softmax_rows(x.data_ptr(), x.scalar_type() == at::kBFloat16, out.data_ptr(),
@@ -79,8 +81,10 @@ void softmax_rows(const at::Tensor& x, at::Tensor out) {
 void resize_bilinear_nhwc(const at::Tensor& x, at::Tensor out, int64_t mode) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous() && x.dim() == 4 &&
               x.size(3) % 8 == 0, "resize_bilinear_nhwc: x bf16 NHWC, C % 8 == 0");
-  TORCH_CHECK(out.scalar_type() == at::kBFloat16 && out.is_contiguous() && out.size(0) == x.size(0) &&
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 && out.is_contiguous() && out.dim() == 4 && out.size(0) == x.size(0) &&
               out.size(3) == x.size(3), "resize_bilinear_nhwc: out");
+  TORCH_CHECK(out.is_cuda() && out.device() == x.device(), "resize_bilinear_nhwc: out must be on the GPU of x");
+  TORCH_CHECK(mode >= 0 && mode <= 3, "resize_bilinear_nhwc: mode 0..3");
   const at::DeviceGuard g(x.device());
   CHECK_HIP_O(lumen::resize_bilinear_nhwc(reinterpret_cast<const uint16_t*>(x.data_ptr()),
                                           reinterpret_cast<uint16_t*>(out.data_ptr()), (int)x.size(0),
@@ -94,6 +98,7 @@ void bmm(const at::Tensor& a, const at::Tensor& b, at::Tensor c) {
               c.scalar_type() == at::kFloat, "bmm: 3-D f32/bf16 operands, f32 out");
   TORCH_CHECK(a.size(0) == b.size(0) && a.size(2) == b.size(1) && c.size(0) == a.size(0) && c.size(1) == a.size(1) &&
               c.size(2) == b.size(2), "bmm: shapes");
+  TORCH_CHECK(c.is_cuda() && c.device() == a.device() && b.device() == a.device(), "bmm: c must be on the GPU of a / b");
   lumen::BmmArgs p{};
   p.a = a.data_ptr(); p.b = b.data_ptr(); p.c = c.data_ptr<float>();
   p.sab = a.stride(0); p.sam = a.stride(1); p.sak = a.stride(2);
@@ -108,6 +113,8 @@ void bmm(const at::Tensor& a, const at::Tensor& b, at::Tensor c) {
 void ew_unary(const at::Tensor& x, at::Tensor out, int64_t op, double p0, double p1) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && out.is_contiguous() && fp_ok(x) && fp_ok(out) &&
               x.numel() == out.numel(), "ew_unary: contiguous f32/bf16");
+  TORCH_CHECK(out.is_cuda() && out.device() == x.device(), "ew_unary: out must be on the GPU of x");
+  TORCH_CHECK(op >= 0 && op <= 16, "ew_unary: op 0..16");
   const at::DeviceGuard g(x.device());
   CHECK_HIP_O(lumen::ew_unary(x.data_ptr(), x.scalar_type() == at::kBFloat16, out.data_ptr(),
                               out.scalar_type() == at::kBFloat16, x.numel(), (int)op, (float)p0, (float)p1, cur()));

@@ -556,11 +556,14 @@ class OnnxGraph:
             f = {"Add": torch.add, "Sub": torch.sub, "Mul": torch.mul, "Div": torch.div, "Pow": torch.pow,
                  "Max": torch.maximum, "Min": torch.minimum, "Equal": torch.eq, "Greater": torch.gt,
                  "Less": torch.lt}[op]
-            x, y = t[0], t[1]
-            if x.is_floating_point() != y.is_floating_point():
-                y = y.to(x.dtype) if x.is_floating_point() else y
-                x = x.to(y.dtype)
-            return out(f(x, y))
+            xs = list(t) if op in ("Max", "Min") else t[:2]      # Max / Min are variadic
+            fl = [x for x in xs if x.is_floating_point()]
+            if fl and len(fl) != len(xs):
+                xs = [x if x.is_floating_point() else x.to(fl[0].dtype) for x in xs]
+            r = xs[0]
+            for y in xs[1:]:
+                r = f(r, y)
+            return out(r)
         if op == "BatchNormalization":
             sc, bi, mu, var = (x.view(1, -1, 1, 1) if t[0].dim() == 4 else x for x in t[1:5])
             return out((t[0] - mu) / torch.sqrt(var + float(a.get("epsilon", 1e-5))) * sc + bi)
@@ -585,8 +588,13 @@ class OnnxGraph:
                 pp = (p[0], p[1])
             if op == "MaxPool":
                 return out(F.max_pool2d(x, k, s, pp, ceil_mode=bool(a.get("ceil_mode", 0))))
-            return out(F.avg_pool2d(x, k, s, pp, ceil_mode=bool(a.get("ceil_mode", 0)),
-                                    count_include_pad=bool(a.get("count_include_pad", 0))))
+            cip, ceil = bool(a.get("count_include_pad", 0)), bool(a.get("ceil_mode", 0))
+            if pp == (0, 0) and any(p) and not cip:
+                # asymmetric pads were applied as zeros above: divide by the count of real pixels
+                ones = F.pad(torch.ones_like(t[0][:1, :1]), (p[1], p[3], p[0], p[2]))
+                return out(F.avg_pool2d(x, k, s, 0, ceil_mode=ceil, divisor_override=1) /
+                           F.avg_pool2d(ones, k, s, 0, ceil_mode=ceil, divisor_override=1))
+            return out(F.avg_pool2d(x, k, s, pp, ceil_mode=ceil, count_include_pad=cip))
         if op == "GlobalAveragePool":
             return out(t[0].mean(dim=(2, 3), keepdim=True))
         if op == "GlobalMaxPool":
@@ -617,14 +625,16 @@ class OnnxGraph:
         if op == "Unsqueeze":
             axes = a.get("axes") if "axes" in a else t[1].tolist()
             x = t[0]
-            for ax in sorted(int(q) for q in axes):
-                x = x.unsqueeze(ax if ax >= 0 else x.dim() + 1 + ax)
+            rank = x.dim() + len(axes)                   # negative axes count from the OUTPUT rank
+            for ax in sorted(int(q) % rank for q in axes):
+                x = x.unsqueeze(ax)
             return out(x)
         if op == "Shape":        # host-side: shape arithmetic never launches device kernels
             return out(torch.tensor(list(t[0].shape), dtype=torch.int64))
         if op == "Gather":
             ax = int(a.get("axis", 0))
-            idx = t[1].long()
+            idx = t[1].long().to(t[0].device)
+            idx = torch.where(idx < 0, idx + t[0].shape[ax], idx)      # negative indices count from the end
             r = torch.index_select(t[0], ax, idx.reshape(-1)).reshape(
                 *t[0].shape[:ax], *idx.shape, *t[0].shape[ax + 1:])
             return out(r)
@@ -634,12 +644,19 @@ class OnnxGraph:
             axes = t[3].tolist() if len(t) > 3 and t[3] is not None else list(range(len(starts)))
             steps = t[4].tolist() if len(t) > 4 and t[4] is not None else [1] * len(starts)
             sl = [slice(None)] * x.dim()
+            rev = []
             for s0, e0, ax, st in zip(starts, ends, axes, steps):
                 dimn = x.shape[ax]
-                s0 = max(0, min(dimn, s0 + dimn if s0 < 0 else s0))
-                e0 = max(0, min(dimn, e0 + dimn if e0 < 0 else e0))
-                sl[ax] = slice(s0, e0, st)
-            return out(x[tuple(sl)])
+                s0 = s0 + dimn if s0 < 0 else s0
+                e0 = e0 + dimn if e0 < 0 else e0
+                if st > 0:
+                    sl[ax] = slice(max(0, min(dimn, s0)), max(0, min(dimn, e0)), st)
+                else:       # negative step: start clamps to [0, dim - 1], end to [-1, dim - 1]
+                    rev.append((ax, torch.arange(max(0, min(dimn - 1, s0)), max(-1, min(dimn - 1, e0)), st)))
+            x = x[tuple(sl)]
+            for ax, idx in rev:
+                x = x.index_select(ax, idx.to(x.device))
+            return out(x)
         if op == "Cast":
             to = ox.DTYPES.get(int(a["to"]), np.float32)
             return out(t[0].to(torch.from_numpy(np.zeros(0, to)).dtype))
@@ -652,7 +669,14 @@ class OnnxGraph:
             return out(c.to(self.device) if c.is_floating_point() else c)
         if op == "ReduceMean":
             axes = a.get("axes", None)
-            return out(t[0].mean(dim=tuple(axes), keepdim=bool(a.get("keepdims", 1))) if axes else t[0].mean())
+            if axes is None and len(t) > 1 and t[1] is not None:      # opset 18: axes is the second input
+                axes = [int(q) for q in t[1].reshape(-1).tolist()]
+            keep = bool(a.get("keepdims", 1))
+            if axes:
+                return out(t[0].mean(dim=tuple(axes), keepdim=keep))
+            if a.get("noop_with_empty_axes", 0):
+                return out(t[0])
+            return out(t[0].mean(dim=tuple(range(t[0].dim())), keepdim=keep))
         if op == "LayerNormalization":
             ax = int(a.get("axis", -1)) % t[0].dim()
             shape = t[0].shape[ax:]
@@ -686,6 +710,11 @@ class OnnxGraph:
             return [_V(self._unary(t[0], _UNARY[op], p0, p1))]
         if op in _BINARY and len(t) == 2 and (fp[0] or fp[1]):
             return [_V(self._binary(t[0], t[1], _BINARY[op]))]
+        if op in ("Max", "Min") and len(t) > 2 and all(fp):     # variadic: a chain of binary launches
+            y = self._binary(t[0], t[1], _BINARY[op])
+            for z in t[2:]:
+                y = self._binary(y, z, _BINARY[op])
+            return [_V(y)]
         if op == "PRelu" and fp[0]:
             sl = t[1]
             if sl.dim() == 1 and t[0].dim() == 4:
@@ -757,8 +786,35 @@ class OnnxGraph:
         size = tuple(sizes[2:]) if sizes else (int(x.shape[2] * scales[2]), int(x.shape[3] * scales[3]))
         if mode == "nearest":
             return F.interpolate(x, size=size, mode="nearest")
-        align = a.get("coordinate_transformation_mode", "half_pixel") == "align_corners"
-        return F.interpolate(x, size=size, mode="bilinear", align_corners=align)
+        ctm = a.get("coordinate_transformation_mode", "half_pixel")
+        if ctm not in _RESIZE_MODES:
+            raise NotImplementedError(f"ONNX Resize: linear coordinate_transformation_mode {ctm!r} is not supported")
+
+        def taps(osz: int, isz: int):
+            # source coordinate per output index, clamped to [0, in - 1]: the same map as
+            # resize_bilinear_nhwc_kernel (csrc/onnx_ops.hip)
+            o = torch.arange(osz, dtype=torch.float64)
+            if ctm == "align_corners":
+                f = o * ((isz - 1) / (osz - 1)) if osz > 1 else torch.zeros(osz, dtype=torch.float64)
+            elif ctm == "asymmetric":
+                f = o * (isz / osz)
+            elif ctm == "pytorch_half_pixel" and osz == 1:
+                f = torch.zeros(osz, dtype=torch.float64)
+            else:
+                f = (o + 0.5) * (isz / osz) - 0.5
+            f = f.clamp(0, isz - 1)
+            i0 = f.floor().long()
+            i1 = (i0 + 1).clamp(max=isz - 1)
+            return i0.to(x.device), i1.to(x.device), (f - i0).to(x.device, x.dtype)
+
+        y0, y1, wy = taps(size[0], x.shape[2])
+        x0, x1, wx = taps(size[1], x.shape[3])
+        wy = wy[:, None]
+
+        def row(v):
+            return v[..., x0] * (1 - wx) + v[..., x1] * wx
+
+        return row(x[:, :, y0]) * (1 - wy) + row(x[:, :, y1]) * wy
 
     def _matmul(self, n, t):
         a = n.attrs

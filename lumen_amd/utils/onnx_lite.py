@@ -324,8 +324,9 @@ def _vi(f: int, x: int) -> bytes:
 
 
 def _tensor_bytes(name: str, a: np.ndarray) -> bytes:
+    shape = np.shape(a)             # ascontiguousarray turns a 0-dim array into shape (1,)
     a = np.ascontiguousarray(a)
-    out = b"".join(_vi(1, d) for d in a.shape)
+    out = b"".join(_vi(1, d) for d in shape)
     out += _vi(2, NP2ONNX[a.dtype])
     out += _ld(8, name.encode())
     out += _ld(9, a.astype(a.dtype.newbyteorder("<")).tobytes())
