@@ -338,12 +338,18 @@ void sample_rows(const at::Tensor& logits, const at::Tensor& inv_t, const at::Te
 // sequence [B]; u, in_ids and tok per row [B * T].  Row (b, i) is penalised over b's bitmap slot and
 // in_ids[b * T .. b * T + i]; tok of a dead row is -1.  verify_accept then writes n_acc int32 [B]
 // and marks in_ids[b * T .. b * T + n_acc[b]] in the slot -- the draw itself marks nothing.
+// Guided form: all seven guide tensors or none, as for sample_rows, but g_in is int32 [B * T]: the
+// grammar state in which each row draws (-1: unguided).  g_slot and g_state are neither read nor
+// written.
 void sample_verify_rows(const at::Tensor& logits, int64_t T, const at::Tensor& n_rows, const at::Tensor& inv_t,
                         const at::Tensor& top_p, const at::Tensor& penalty, const at::Tensor& u,
                         const at::Tensor& greedy, const at::Tensor& seen_slot, at::Tensor seen,
                         const at::Tensor& in_ids, at::Tensor tok, at::Tensor n_acc,
                         const c10::optional<at::Tensor>& out_v, const c10::optional<at::Tensor>& out_i,
-                        const c10::optional<at::Tensor>& out_lse) {
+                        const c10::optional<at::Tensor>& out_lse, const c10::optional<at::Tensor>& g_allow,
+                        const c10::optional<at::Tensor>& g_dfa, const c10::optional<at::Tensor>& tok_off,
+                        const c10::optional<at::Tensor>& tok_dat, const c10::optional<at::Tensor>& g_slot,
+                        const c10::optional<at::Tensor>& g_in, const c10::optional<at::Tensor>& g_state) {
   TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat && logits.dim() == 2 && logits.stride(1) == 1,
               "sample_verify_rows: logits f32 [B * T, V]");
   const int64_t R = logits.size(0), V = logits.size(1);
@@ -388,6 +394,33 @@ void sample_verify_rows(const at::Tensor& logits, int64_t T, const at::Tensor& n
     vec(*out_lse, at::kFloat, R, "out_lse f32 [B * T]");
     a.out_lse = out_lse->data_ptr<float>();
   }
+  auto has = [](const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); };
+  const int ng = has(g_allow) + has(g_dfa) + has(tok_off) + has(tok_dat) + has(g_slot) + has(g_in) + has(g_state);
+  TORCH_CHECK(ng == 0 || ng == 7, "sample_verify_rows: the guide tensors come together");
+  if (ng == 7) {
+    auto dev = [&](const at::Tensor& t, at::ScalarType ty, const char* what) {
+      TORCH_CHECK(t.is_cuda() && t.device() == logits.device() && t.scalar_type() == ty && t.is_contiguous(),
+                  "sample_verify_rows: ", what);
+    };
+    dev(*g_allow, at::kInt, "g_allow int32 [A, ceil(V / 32)]");
+    dev(*g_dfa, at::kShort, "g_dfa int16 [A, 256]");
+    dev(*tok_off, at::kInt, "tok_off int32 [V + 1]");
+    dev(*tok_dat, at::kByte, "tok_dat uint8");
+    dev(*g_state, at::kInt, "g_state int32 [S]");
+    dev(*g_slot, at::kInt, "g_slot int32 (not read)");
+    vec(*g_in, at::kInt, R, "g_in int32 [B * T]");
+    const int64_t A = g_allow->dim() == 2 ? g_allow->size(0) : 0;
+    TORCH_CHECK(A >= 1 && A <= 32767 && g_allow->size(1) == words,
+                "sample_verify_rows: g_allow int32 [A, ceil(V / 32)], A < 2^15");
+    TORCH_CHECK(g_dfa->dim() == 2 && g_dfa->size(0) == A && g_dfa->size(1) == 256,
+                "sample_verify_rows: g_dfa int16 [A, 256]");
+    TORCH_CHECK(tok_off->numel() == V + 1, "sample_verify_rows: tok_off int32 [V + 1]");
+    TORCH_CHECK(g_state->numel() >= 1, "sample_verify_rows: g_state int32 [S]");
+    a.g_allow = g_allow->data_ptr<int>(); a.g_dfa = g_dfa->data_ptr<int16_t>();
+    a.tok_off = tok_off->data_ptr<int>(); a.tok_dat = tok_dat->data_ptr<uint8_t>();
+    a.g_slot = g_slot->data_ptr<int>(); a.g_in = g_in->data_ptr<int>(); a.g_state = g_state->data_ptr<int>();
+    a.g_A = (int)A; a.g_S = (int)g_state->numel();
+  }
   const at::DeviceGuard g(logits.device());
   const int64_t nws = lumen::sample_ws_floats((int)R, (int)V);
   at::Tensor ws;
@@ -431,7 +464,9 @@ TORCH_LIBRARY_FRAGMENT(lumen, m) {
         "Tensor(g!)? g_state=None) -> ()");
   m.def("sample_verify_rows(Tensor logits, int T, Tensor n_rows, Tensor inv_t, Tensor top_p, Tensor penalty, Tensor u, "
         "Tensor greedy, Tensor seen_slot, Tensor(s!) seen, Tensor in_ids, Tensor(t!) tok, Tensor(n!) n_acc, "
-        "Tensor(v!)? out_v=None, Tensor(i!)? out_i=None, Tensor(l!)? out_lse=None) -> ()");
+        "Tensor(v!)? out_v=None, Tensor(i!)? out_i=None, Tensor(l!)? out_lse=None, Tensor? g_allow=None, "
+        "Tensor? g_dfa=None, Tensor? tok_off=None, Tensor? tok_dat=None, Tensor? g_slot=None, Tensor? g_in=None, "
+        "Tensor? g_state=None) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(lumen, CUDA, m) {

@@ -34,17 +34,21 @@ struct SampleArgs {
   int T;
   const int* n_rows;        // [B] live rows of each sequence (a dead row writes tok = -1 only)
   int* n_acc;               // [B] out: accepted draft tokens; in_ids 0 .. n_acc are marked in the slot
-  // Guided form (decode form only; all null / zero when unused): a row whose grammar state s is
+  // Guided form (all null / zero when unused): a row whose grammar state s is
   // >= 0 draws among the tokens whose bit is set in g_allow[s], and lane 0 then walks the drawn
   // token's bytes through g_dfa from s and stores the new state.  s = g_in[b] when that is >= 0
   // (a step fed by the host), else g_state[g_slot[b]] (a look-ahead step, straight after the step
   // that wrote it).  g_slot[b] = -1: an unguided row of a guided batch.
+  // Verify form, guided (T > 0): g_in has B * T entries, entry b * T + i the state in which row
+  // (b, i) draws (the host walks the draft tokens), -1 an unguided row; a state outside the arena
+  // allows nothing.  All guide arguments must still be set, but g_slot, g_state, g_dfa and the token
+  // bytes are not read and nothing is stored: no state is kept on the device between verify steps.
   const int* g_allow;       // [A, words] arena of allowed-token bitmaps, one row per grammar state
   const int16_t* g_dfa;     // [A, 256] byte transitions in arena-global state ids, -1 = dead
   const int* tok_off;       // [V + 1] CSR of the token bytes ...
   const uint8_t* tok_dat;   // ... and the bytes
   const int* g_slot;        // [B] row of g_state the sequence owns, or -1
-  const int* g_in;          // [B] the state fed by the host, or -1: read g_state[g_slot]
+  const int* g_in;          // [B] the state fed by the host, or -1: read g_state[g_slot]; verify form: [B * T]
   int* g_state;             // [g_S] the states the device keeps between look-ahead steps
   int g_A, g_S;
 };

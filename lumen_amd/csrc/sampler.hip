@@ -31,12 +31,19 @@
 // row before them and marks the inputs up to the last accepted one -- a rejected draft token never
 // reaches the bitmap.
 //
-// Guided form (template flag GUIDED, decode form only; the other instantiations are compiled as
-// before): a row with a grammar state s >= 0 stages row s of the arena of allowed-token bitmaps
+// Guided form (template flag GUIDED; the other instantiations are compiled as before): a row with a grammar state s >= 0 stages row s of the arena of allowed-token bitmaps
 // into a second LDS array, chunked like the seen bitmap, and a logit whose bit is clear becomes
 // -inf before the penalty and the 1/T: it is never a candidate and adds nothing to the
 // log-sum-exp, so the allowed set is renormalised.  After the draw lane 0 walks the drawn token's
 // bytes through the byte DFA from s and stores the new state, which the look-ahead step reads.
+//
+// Verify form, guided (VERIFY and GUIDED): the guide is per row.  g_in has B * T entries, entry
+// b * T + i the arena-global state in which row (b, i) draws -- the state after sequence b's text and
+// its draft tokens 1 .. i, which the host computes -- or -1 for an unguided row; a state outside the
+// arena allows nothing (tok = -1).  The row's allow row is staged like the decode form's and GuideXf
+// wraps the SeenXf whose bitmap has the inputs 0 .. i OR-ed in.  This form reads and writes neither
+// g_slot nor g_state and walks no DFA: every step around a verify step is fed by the host, so
+// nothing would read a stored state, and verify_accept is the unguided form's.
 #include "sampler.h"
 
 #include <type_traits>
@@ -102,7 +109,6 @@ template <int MODE, bool VERIFY, bool GUIDED = false>
 __global__ void __launch_bounds__(256)
 sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__ ci, float* __restrict__ pml,
                    int nch) {
-  static_assert(!(VERIFY && GUIDED), "the verify form is not guided");
   __shared__ int bits[SAMPLE_STAGE_WORDS];
   __shared__ int allow[GUIDED ? SAMPLE_STAGE_WORDS : 1];   // 2 KB more in the guided form; unused (and dropped) otherwise
   const int row = blockIdx.x;
@@ -121,9 +127,13 @@ sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__
   const int k = a.greedy[seq] && !a.out_v ? 1 : SAMPLE_K;
   // guided: the row's slot of g_state and its grammar state (-1: unguided row; a state outside the
   // arena allows nothing).  Every thread reads the state before the first barrier, lane 0 stores the
-  // new one after the last.
+  // new one after the last.  The verify form takes the row's state from the host and keeps none.
   int gslot = -1, gs = -1;
-  if constexpr (GUIDED) {
+  if constexpr (GUIDED && VERIFY) {
+    gs = a.g_in[row];
+    if (gs < 0) gs = -1;
+    else if (gs >= a.g_A) gs = a.g_A;
+  } else if constexpr (GUIDED) {
     gslot = a.g_slot[row];
     if (gslot >= a.g_S) gslot = -1;
     if (gslot >= 0) {
@@ -216,7 +226,7 @@ sample_rows_kernel(const SampleArgs a, float* __restrict__ cv, int* __restrict__
         *w = *w | (int)(1u << (in_id & 31));
       }
     }
-    if constexpr (GUIDED) {
+    if constexpr (GUIDED && !VERIFY) {
       // the slot belongs to this sequence: plain loads and a plain store.  An EOS or zero-length
       // token has no bytes and leaves the state; so does tok = -1.  The drawn token's bit was set, so
       // the walk stays alive; a walk that does not (a token outside every table) keeps the state too.
@@ -286,16 +296,17 @@ static hipError_t launch_rows(const SampleArgs& a, int R, float* ws, hipStream_t
 hipError_t sample_rows(const SampleArgs& a, float* ws, hipStream_t stream) {
   if (a.B == 0) return hipSuccess;
   if (a.V < SAMPLE_K || a.words != (a.V + 31) / 32) return hipErrorInvalidValue;
-  if (a.g_slot != nullptr) {   // the guided form: every guide argument, and the decode form only
-    if (a.T != 0 || a.g_allow == nullptr || a.g_dfa == nullptr || a.tok_off == nullptr || a.tok_dat == nullptr ||
-        a.g_in == nullptr || a.g_state == nullptr || a.g_A < 1 || a.g_S < 1)
-      return hipErrorInvalidValue;
-    return launch_rows<false, true>(a, a.B, ws, stream);
-  }
-  if (a.T == 0) return launch_rows<false>(a, a.B, ws, stream);
+  // the guided form: every guide argument or none (the verify form reads g_allow and g_in only)
+  const bool guided = a.g_slot != nullptr || a.g_in != nullptr || a.g_allow != nullptr || a.g_dfa != nullptr ||
+                      a.tok_off != nullptr || a.tok_dat != nullptr || a.g_state != nullptr;
+  if (guided && (a.g_slot == nullptr || a.g_in == nullptr || a.g_allow == nullptr || a.g_dfa == nullptr ||
+                 a.tok_off == nullptr || a.tok_dat == nullptr || a.g_state == nullptr || a.g_A < 1 || a.g_S < 1))
+    return hipErrorInvalidValue;
+  if (a.T == 0) return guided ? launch_rows<false, true>(a, a.B, ws, stream) : launch_rows<false>(a, a.B, ws, stream);
   if (a.T < 1 || a.T > SAMPLE_VERIFY_MAX_T || a.B > 64 || a.n_rows == nullptr || a.n_acc == nullptr)
     return hipErrorInvalidValue;
-  hipError_t e = launch_rows<true>(a, a.B * a.T, ws, stream);
+  hipError_t e = guided ? launch_rows<true, true>(a, a.B * a.T, ws, stream)
+                        : launch_rows<true>(a, a.B * a.T, ws, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(verify_accept_kernel, dim3(1), dim3(64), 0, stream, a);
   return hipGetLastError();

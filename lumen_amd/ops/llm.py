@@ -495,7 +495,8 @@ def _mark_seen(seen: torch.Tensor, slot: int, t: int) -> None:
 
 
 def sample_verify_rows(logits: torch.Tensor, T: int, n_rows, inv_t, top_p, penalty, u, greedy, seen_slot,
-                       seen: torch.Tensor, in_ids, candidates: bool = True):
+                       seen: torch.Tensor, in_ids, candidates: bool = True, *,
+                       guide: Optional[GuideTensors] = None):
     """The verify form of :func:`sample_rows` (speculative decoding of sampled / penalised requests):
     fp32 ``logits`` [B * T, V], row ``b * T + i`` holding the logits after input ``i`` of sequence ``b``
     -- ``in_ids[b * T]`` is its last token, the next ones its draft tokens -- and live while
@@ -512,7 +513,15 @@ def sample_verify_rows(logits: torch.Tensor, T: int, n_rows, inv_t, top_p, penal
     Returns ``(v [B*T, 64], i [B*T, 64], lse [B*T], tok [B*T] int32, n_acc [B] int32, seen)``; dead
     rows of ``v, i, lse`` are unspecified on the GPU (-inf, -1, 0 on the CPU).  ``candidates=False``
     on the GPU: ``v, i, lse`` are None.  CPU tensors run the reference of :func:`sample_rows` row
-    by row."""
+    by row.
+
+    ``guide`` (:class:`GuideTensors`): the guided verify form.  ``guide.g_in`` has B * T entries:
+    entry ``b * T + i`` is the grammar state (a row of ``guide.allow``) in which row (b, i) draws --
+    the state after sequence b's text and its draft tokens 1 .. i, which the caller walks -- or -1
+    for an unguided row.  A live row with a state is masked by the state's allow row exactly as
+    :func:`mask_logits_` masks with -inf and then drawn as above; a state outside the arena allows
+    nothing (``tok = -1``).  ``guide.slot`` and ``guide.state`` are ignored and left untouched (no
+    state is kept between verify steps), and the result has the same six elements."""
     d = logits.device
     T = int(T)
     R, V = logits.shape
@@ -535,8 +544,15 @@ def sample_verify_rows(logits: torch.Tensor, T: int, n_rows, inv_t, top_p, penal
         v = torch.empty((R, SAMPLE_K), dtype=torch.float32, device=d) if candidates else None
         i = torch.empty((R, SAMPLE_K), dtype=torch.int32, device=d) if candidates else None
         lse = torch.empty(R, dtype=torch.float32, device=d) if candidates else None
-        hip_ops().sample_verify_rows(logits, T, n_rows, inv_t, top_p, penalty, u, greedy, seen_slot, seen, in_ids,
-                                     tok, n_acc, v, i, lse)
+        if guide is not None:
+            g_in = as_t(guide.g_in, torch.int32, R)
+            g_slot = torch.as_tensor(guide.slot, dtype=torch.int32, device=d).reshape(-1).contiguous()   # not read
+            hip_ops().sample_verify_rows(logits, T, n_rows, inv_t, top_p, penalty, u, greedy, seen_slot, seen,
+                                         in_ids, tok, n_acc, v, i, lse, guide.allow, guide.dfa, guide.tok_off,
+                                         guide.tok_dat, g_slot, g_in, guide.state)
+        else:
+            hip_ops().sample_verify_rows(logits, T, n_rows, inv_t, top_p, penalty, u, greedy, seen_slot, seen,
+                                         in_ids, tok, n_acc, v, i, lse)
         return v, i, lse, tok, n_acc, seen
     v = torch.full((R, SAMPLE_K), float("-inf"))
     i = torch.full((R, SAMPLE_K), -1, dtype=torch.int32)
@@ -544,6 +560,8 @@ def sample_verify_rows(logits: torch.Tensor, T: int, n_rows, inv_t, top_p, penal
     tok = torch.full((R,), -1, dtype=torch.int32)
     n_acc = torch.zeros(B, dtype=torch.int32)
     feed = in_ids.tolist()
+    gin = as_t(guide.g_in, torch.int32, R).tolist() if guide is not None else [-1] * R
+    one = torch.zeros(1, dtype=torch.int32)      # the row reference's state array: a scratch row per call
     for b in range(B):
         n = min(int(n_rows[b]), T)
         slot = int(seen_slot[b])
@@ -553,8 +571,11 @@ def sample_verify_rows(logits: torch.Tensor, T: int, n_rows, inv_t, top_p, penal
         tmp = seen[slot:slot + 1].clone() if own else seen[:0]
         for q in range(n):
             r = b * T + q
+            # a row with a state: the decode form's guided reference on that one row, fed the state
+            gr = None if gin[r] < 0 else guide._replace(slot=[0], g_in=[gin[r]], state=one.clone())
             rv, ri, rl, rt, tmp = sample_rows(logits[r:r + 1], inv_t[b:b + 1], top_p[b:b + 1], penalty[b:b + 1],
-                                              u[r:r + 1], greedy[b:b + 1], [0 if own else -1], tmp, in_ids[r:r + 1])
+                                              u[r:r + 1], greedy[b:b + 1], [0 if own else -1], tmp, in_ids[r:r + 1],
+                                              guide=gr)[:5]
             v[r], i[r], lse[r], tok[r] = rv[0], ri[0], rl[0], rt[0]
         j = 0
         while j < n - 1 and int(tok[b * T + j]) == feed[b * T + j + 1]:

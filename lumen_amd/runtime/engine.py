@@ -34,9 +34,16 @@ host<->device every token (packages/lumen-vlm/src/lumen_vlm/backends/onnxrt_back
   the device sampler masks the logits by the row of the request's grammar state and advances the
   state itself, so look-ahead stays on; the host keeps the same state for the steps it feeds and
   for the host sampling path.  Such a request ends with reason ``stop`` at EOS, or ``length`` when
-  ``max_new_tokens`` cuts it -- its text may then be an incomplete match.  Not with speculative
-  decoding (a batch with a guided request takes no verify steps) and not under tensor parallelism
-  (``submit`` raises).
+  ``max_new_tokens`` cuts it -- its text may then be an incomplete match.  Not under tensor
+  parallelism (``submit`` raises);
+* speculative decoding of guided requests (``spec_guided`` / ``LUMEN_SPEC_GUIDED=1``, off by default;
+  without it a batch with a guided request takes no verify steps): a guided request drafts the
+  tokens its grammar forces (:meth:`Guide.forced`: where the DFA has one live byte transition the
+  continuation is known before the model runs), else the drafter's proposal cut at the first token
+  the grammar does not allow.  Such a batch always takes the sampled verify form, through the
+  ``verify_guided`` graphs: every row is masked by the grammar state it would be in if the draft
+  tokens before it had been accepted, which the host walks and feeds.  The switch alone, without a
+  drafter, speculates on the forced tokens only.
 
 Tensor parallelism: rank 0 runs this loop and broadcasts every step (prefill inputs,
 decode token ids / positions / slots / block tables) to follower ranks running
@@ -108,6 +115,7 @@ class GenRequest:
     hist: Optional[list] = None             # ... prompt ids + tokens, as the drafter sees them
     hist0: int = 0                          # ... prompt ids in hist
     draft: tuple = (-1, ())                 # ... (len(tokens) it was made for, proposal)
+    draft_forced: bool = False              # ... the proposal is the grammar's forced tokens (guided request)
     gstate: int = -1                        # guided decoding: the grammar state after ``tokens`` (host side)
     guide_slot: Optional[int] = None        # ... row of the device's state array
     guide_base: Optional[int] = None        # ... first arena row of the request's guide
@@ -576,6 +584,12 @@ class DecodeGraphs(SeenSlots):
     the drawn token of every row, the accepted draft tokens of every sequence and the error word.
     Padded sequences are greedy with slot -1 and one live row.
 
+    ``mode="verify_guided"`` graphs are the ``verify_sample`` graphs with the sampler's guided verify
+    form, for batches with a guided request (speculative decoding of guided requests): the step
+    buffer also carries ``g_in`` of Bp * T rows, the arena-global grammar state in which each row
+    draws (-1 for an unguided, dead or padded row).  No state is kept on the device between verify
+    steps.  They need :attr:`arena` like the ``guided`` graphs.
+
     ``mode="guided"`` graphs are the ``sample`` graphs with the sampler's guided form: the step
     buffer also carries per row the sequence's row of the device's grammar states (``g_slot``, -1
     for an unguided or padded row) and the state the host feeds (``g_in``, -1 on a look-ahead step,
@@ -892,11 +906,24 @@ class DecodeGraphs(SeenSlots):
         lay["bytes"] = -(-o // 16) * 16
         return lay
 
-    def _capture_verify(self, Bp: int, W: int, T: int, sample: bool = False) -> dict:
+    @staticmethod
+    def _layout_verify_guided(Bp: int, W: int, T: int) -> dict:
+        """the verify_sample layout followed by g_in i32 of Bp * T rows"""
+        lay = dict(DecodeGraphs._layout_verify_sample(Bp, W, T))
+        lay["g_in"] = (lay["bytes"], Bp * T)
+        lay["bytes"] = -(-(lay["bytes"] + 4 * Bp * T) // 16) * 16
+        return lay
+
+    def _capture_verify(self, Bp: int, W: int, T: int, sample: bool = False, guided: bool = False) -> dict:
         """``sample``: the ``verify_sample`` graph -- the device sampler's verify form and its accept
-        kernel in place of the row arg-max; ``res`` = tok [Bp * T], n_acc [Bp] and the error word"""
+        kernel in place of the row arg-max; ``res`` = tok [Bp * T], n_acc [Bp] and the error word.
+        ``guided``: the ``verify_guided`` graph -- the same with the sampler's guided verify form"""
         d = self.llm.embed.device
-        lay = self._layout_verify_sample(Bp, W, T) if sample else self._layout_verify(Bp, W, T)
+        sample = sample or guided
+        if guided and self.arena is None:
+            raise RuntimeError("guided graphs need the guide arena")
+        lay = self._layout_verify_guided(Bp, W, T) if guided else self._layout_verify_sample(Bp, W, T) if sample \
+            else self._layout_verify(Bp, W, T)
         R, k = Bp * T, self.K_GREEDY
         dbuf = torch.zeros(lay["bytes"], dtype=torch.uint8, device=d)
 
@@ -911,6 +938,9 @@ class DecodeGraphs(SeenSlots):
                 for name, dt in self._SAMPLE_ROWS.items():
                     o, n = lay[name]
                     v[name] = buf[o:o + dt.itemsize * n].view(dt)
+            if guided:
+                o, n = lay["g_in"]
+                v["g_in"] = buf[o:o + 4 * n].view(torch.int32)
             return v
 
         st = views(dbuf)
@@ -923,13 +953,19 @@ class DecodeGraphs(SeenSlots):
                 st[name].fill_(pad)
             res = torch.zeros(R + Bp + 1, dtype=torch.int32, device=d)
             seen = self._seen()
+            gargs = ()
+            if guided:
+                st["g_in"].fill_(-1)
+                ar = self.arena
+                # the guided verify form reads the arena's allow rows and g_in; the slot argument is not read
+                gargs = (ar.allow, ar.dfa, ar.tok_off, ar.tok_dat, st["g_in"], st["g_in"], ar.state)
 
             def run():
                 logits = self.llm.verify(st["ids"], st["pos"], st["slots"], self.kv, st["bt"], st["ctx"], st["n_rows"],
                                          T, workspace=ws)
                 ops.hip_ops().sample_verify_rows(logits, T, st["n_rows"], st["inv_t"], st["top_p"], st["penalty"],
                                                  st["u"], st["greedy"], st["seen_slot"], seen, st["ids"], res[:R],
-                                                 res[R:R + Bp], None, None, None)
+                                                 res[R:R + Bp], None, None, None, *gargs)
                 return logits
         else:
             res = torch.zeros(R + 1, dtype=torch.int32, device=d)          # arg-max token per row + the error word
@@ -945,7 +981,7 @@ class DecodeGraphs(SeenSlots):
 
         g, out = self._record(run, d)
         pin = lambda t: torch.empty(t.shape, dtype=t.dtype).pin_memory()  # noqa: E731
-        mode = "verify_sample" if sample else "verify"
+        mode = "verify_guided" if guided else "verify_sample" if sample else "verify"
         ent = {"g": g, "st": st, "dbuf": dbuf, "out": out, "ws": ws, "res": res, "lay": lay, "Bp": Bp, "W": W, "T": T,
                "h_step": [pin(dbuf) for _ in range(2)], "h_res": [pin(res) for _ in range(2)],
                "ev": [None, None], "par": 0, "mode": mode}
@@ -953,18 +989,21 @@ class DecodeGraphs(SeenSlots):
         self.graphs[(Bp, W, mode)] = ent
         return ent
 
-    def _entry_verify(self, B: int, width: int, T: int, sample: bool = False) -> dict:
-        key = (self.verify_bucket(B, T), self._width(width), "verify_sample" if sample else "verify")
+    def _entry_verify(self, B: int, width: int, T: int, sample: bool = False, guided: bool = False) -> dict:
+        key = (self.verify_bucket(B, T), self._width(width),
+               "verify_guided" if guided else "verify_sample" if sample else "verify")
         e = self.graphs.get(key)
-        return e if e is not None and e["T"] == T else self._capture_verify(key[0], key[1], T, sample)
+        return e if e is not None and e["T"] == T else self._capture_verify(key[0], key[1], T, sample, guided)
 
     def launch_verify(self, ids, pos, slots, bt, ctx, n_rows, T: int, sample: Optional[dict] = None) -> dict:
         """Stage + replay one verify step: ids / pos / slots host arrays of B * T rows
         (sequence-major, padding rows slot -1), ctx / n_rows of B sequences.  Returns a handle
         for :meth:`verified`.  ``sample``: the device sampler's arrays (keys of ``_SAMPLE_ROWS``;
-        ``u`` of B * T rows, the others of B sequences) -- the step runs the ``verify_sample`` graph."""
+        ``u`` of B * T rows, the others of B sequences) -- the step runs the ``verify_sample`` graph;
+        with ``g_in`` (B * T rows) too, the ``verify_guided`` graph."""
         B = len(ctx)
-        e = self._entry_verify(B, bt.shape[1], T, sample is not None)
+        guided = sample is not None and "g_in" in sample
+        e = self._entry_verify(B, bt.shape[1], T, sample is not None, guided)
         W = e["W"]
         par = e["par"]
         e["par"] ^= 1
@@ -984,6 +1023,9 @@ class DecodeGraphs(SeenSlots):
             for k, pad in self._SAMPLE_PAD.items():
                 hv[k][:] = pad
                 hv[k][:len(sample[k])] = sample[k]
+            if guided:
+                hv["g_in"][:] = -1
+                hv["g_in"][:B * T] = sample["g_in"]
         e["dbuf"].copy_(e["h_step"][par], non_blocking=True)
         e["g"].replay()
         e["h_res"][par].copy_(e["res"], non_blocking=True)
@@ -994,13 +1036,13 @@ class DecodeGraphs(SeenSlots):
 
     def verified(self, h: dict) -> np.ndarray:
         """tokens [B * T] int32 of a launched verify step -- the arg-max of every row, or what the
-        ``verify_sample`` graph drew (then ``h["n_acc"]`` holds the device's accepted counts [B]) --
+        ``verify_sample`` / ``verify_guided`` graph drew (then ``h["n_acc"]`` holds the device's accepted counts [B]) --
         (waits for it); sets ``h["err"]``"""
         e = h["e"]
         h["ev"].synchronize()
         r = e["h_res"][h["par"]].numpy()
         R = e["Bp"] * e["T"]
-        if e["mode"] == "verify_sample":
+        if e["mode"] in ("verify_sample", "verify_guided"):
             h["n_acc"] = r[R:R + h["B"]]
             h["err"] = int(r[R + e["Bp"]])
         else:
@@ -1019,7 +1061,7 @@ class LLMEngine:
                  use_graphs: Optional[bool] = None, prefill_chunk: Optional[int] = None,
                  follower_args: Optional[Callable[[Any], Any]] = None, ingraph_sampling: Optional[bool] = None,
                  spec_tokens: Optional[int] = None, drafter: Optional[Drafter] = None,
-                 spec_sampling: Optional[bool] = None):
+                 spec_sampling: Optional[bool] = None, spec_guided: Optional[bool] = None):
         """``follower_args``: what the TP followers receive instead of the prefill arguments
         (the VLM strips the image: only rank 0 decodes it and runs the vision tower).
         ``ingraph_sampling``: sampled / penalised requests decode through the graphs' device
@@ -1030,7 +1072,11 @@ class LLMEngine:
         ``spec_tokens`` draft tokens per verify step (None: env ``LUMEN_SPEC_TOKENS``, default 3,
         1 .. 7).
         ``spec_sampling`` (None: env ``LUMEN_SPEC_SAMPLING=1``, default off): batches with sampled
-        or penalised requests take verify steps too, drawn by the device sampler's verify form."""
+        or penalised requests take verify steps too, drawn by the device sampler's verify form.
+        ``spec_guided`` (None: env ``LUMEN_SPEC_GUIDED=1``, default off): batches with guided requests
+        take verify steps, always in the sampled form with the sampler's guided verify form.  A guided
+        request drafts its grammar's forced tokens, else what ``drafter`` proposes cut at the
+        grammar; without a drafter it speculates on the forced tokens alone."""
         self.llm = llm
         self.kv = kv
         self.build = prefill_builder
@@ -1050,7 +1096,7 @@ class LLMEngine:
         self.stats = {"prefills": 0, "prefill_chunks": 0, "decode_steps": 0, "tokens": 0,
                       "prefix_hits": 0, "prefix_tokens": 0, "prefill_tokens": 0,
                       "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0, "spec_sample_steps": 0,
-                      "guided_steps": 0}
+                      "guided_steps": 0, "spec_guided_steps": 0, "spec_forced_drafted": 0, "spec_forced_accepted": 0}
         self._arena: Optional[GuideArena] = None     # guided decoding's device tables, built on first need
         if use_graphs is None:
             use_graphs = os.environ.get("LUMEN_HIP_GRAPHS", "1") == "1"
@@ -1070,10 +1116,13 @@ class LLMEngine:
         if spec_sampling is None:
             spec_sampling = os.environ.get("LUMEN_SPEC_SAMPLING", "0") == "1"
         self.spec_sampling = bool(spec_sampling) and tp_sync is None and not llm.tp.enabled
+        if spec_guided is None:
+            spec_guided = os.environ.get("LUMEN_SPEC_GUIDED", "0") == "1"
+        self.spec_guided = bool(spec_guided) and tp_sync is None and not llm.tp.enabled
         # the seen-token bitmaps: the graphs' own (kept if a capture failure drops the graphs), or
         # a bare set for sampled verify steps without graphs
         self._slots: Optional[SeenSlots] = self.graphs
-        if self._slots is None and self.spec_sampling and self.drafter is not None:
+        if self._slots is None and ((self.spec_sampling and self.drafter is not None) or self.spec_guided):
             self._slots = SeenSlots(llm, max_batch)
         self._thread = threading.Thread(target=self._loop, name=f"lumen-{name}-engine", daemon=True)
         self._thread.start()
@@ -1188,7 +1237,7 @@ class LLMEngine:
         """``r`` enters the running batch; a penalised request takes a zeroed row of the device
         sampler's seen bitmap (none free, or no graphs: its batches sample on the host)"""
         wanted = (self.ingraph_sampling and self.graphs is not None) or \
-            (self.spec_sampling and self.drafter is not None and self._slots is not None)
+            (((self.spec_sampling and self.drafter is not None) or self.spec_guided) and self._slots is not None)
         if wanted and self._penalised(r):
             r.seen_slot = self._slots.take_slot()
             if r.seen_slot is not None:
@@ -1197,16 +1246,19 @@ class LLMEngine:
         self._running.append(r)
 
     def _guide_acquire(self, r: GenRequest) -> None:
-        """a guided request that may decode through the ``guided`` graphs takes its guide's arena
-        rows (uploading the guide on first use) and a row of the device's grammar states.  A guide
-        that does not fit raises GuideError: the caller fails this request only."""
+        """a guided request that may decode through the ``guided`` graphs, or take guided verify steps
+        (``spec_guided``, with or without graphs), takes its guide's arena rows (uploading the guide on
+        first use) and a row of the device's grammar states.  A guide that does not fit raises
+        GuideError: the caller fails this request only."""
         g = r.params.guide
-        if g is None or r.guide_base is not None or self.graphs is None or not self.ingraph_sampling \
-                or not _LOOKAHEAD:
+        if g is None or r.guide_base is not None:
+            return
+        if not self.spec_guided and (self.graphs is None or not self.ingraph_sampling or not _LOOKAHEAD):
             return
         if self._arena is None:
             self._arena = GuideArena(self.llm, self.max_batch, g.token_bytes)
-        self.graphs.arena = self._arena
+        if self.graphs is not None:
+            self.graphs.arena = self._arena
         r.guide_base = self._arena.acquire(g)
         r.guide_slot = self._arena.take_slot()
 
@@ -1441,17 +1493,28 @@ class LLMEngine:
         """a verify step may serve this batch: a drafter is set, single GPU without a step channel,
         every request greedy without repetition penalty, and B * T rows fit the 32-row decode GEMMs.
         With ``spec_sampling`` sampled and penalised requests may take part: the vocabulary holds the
-        sampler's 64 candidates and every penalised request holds a bitmap slot"""
-        if not (self.drafter is not None and self.sync is None and not self.llm.tp.enabled
-                and len(reqs) * self.spec_T <= 32):
+        sampler's 64 candidates and every penalised request holds a bitmap slot.
+        A batch with a guided request takes verify steps only with ``spec_guided`` (a drafter is not
+        needed then: the grammar's forced tokens are a draft), always in the sampled form, whatever
+        ``spec_sampling`` says -- a greedy guided request needs the mask too -- so the sampled form's
+        conditions hold and every guided request holds its guide's arena rows"""
+        guided = self._spec_guided(reqs)
+        if not ((self.drafter is not None or (guided and self.spec_guided)) and self.sync is None
+                and not self.llm.tp.enabled and len(reqs) * self.spec_T <= 32):
             return False
-        if any(r.params.guide is not None for r in reqs):      # guided requests take no verify steps
-            return False
-        if not self._spec_sampled(reqs):
+        if guided and not (self.spec_guided and self._arena is not None
+                           and all(r.guide_base is not None for r in reqs if r.params.guide is not None)):
+            return False      # without the switch guided requests take no verify steps
+        if not guided and not self._spec_sampled(reqs):
             return True
-        return (self.spec_sampling and self._slots is not None and self.llm.Vl >= lops.SAMPLE_K
+        return ((guided or self.spec_sampling) and self._slots is not None and self.llm.Vl >= lops.SAMPLE_K
                 and self.spec_T <= lops.SAMPLE_VERIFY_MAX_T
                 and all(r.seen_slot is not None for r in reqs if self._penalised(r)))
+
+    @staticmethod
+    def _spec_guided(reqs) -> bool:
+        """some request is guided: a verify step of this batch is the guided (sampled) form"""
+        return any(r.params.guide is not None for r in reqs)
 
     def _spec_sampled(self, reqs) -> bool:
         """some request is sampled or penalised: a verify step of this batch is the sampled form"""
@@ -1460,19 +1523,33 @@ class LLMEngine:
     def _draft(self, r: GenRequest) -> tuple:
         """the drafter's proposal for ``r``'s next tokens, cut so that the request neither exceeds
         ``max_new_tokens`` (the step also yields one token of its own) nor leaves its reserved blocks;
-        made once per generated length"""
+        made once per generated length.  A guided request (only drafted with ``spec_guided``) proposes
+        the tokens its grammar forces from the host's state ``r.gstate``; where nothing is forced, the
+        drafter's proposal cut at the first token the grammar does not allow in the state reached so
+        far -- so every row of the verify step has a valid grammar state, which the host knows"""
         n = len(r.tokens)
         if r.draft[0] == n:
             return r.draft[1]
         k = min(self.spec_T - 1, r.params.max_new_tokens - n - 1,
                 len(self.kv.blocks.table(r.rid)) * BLOCK - r.ctx - 1)
         d: tuple = ()
-        if k > 0:
+        g = r.params.guide
+        r.draft_forced = False
+        if k > 0 and g is not None:
+            d = g.forced(r.gstate, k)
+            r.draft_forced = bool(d)
+        if k > 0 and not d and self.drafter is not None:
             if r.hist is None:
                 r.hist = [int(t) for t in r.prompt_ids] if r.prompt_ids is not None else []
                 r.hist0 = len(r.hist)
             r.hist.extend(r.tokens[len(r.hist) - r.hist0:])
             d = tuple(int(t) for t in self.drafter(r.hist, k))[:k]
+            if g is not None:
+                st, ok = r.gstate, 0
+                while ok < len(d) and g.allows(st, d[ok]):
+                    st = g.walk(st, d[ok])
+                    ok += 1
+                d = d[:ok]
         r.draft = (n, d)
         return d
 
@@ -1515,9 +1592,16 @@ class LLMEngine:
         the device sampler's verify form from the row's penalised, scaled logits with the uniform of
         token len(tokens) + i -- what a decode step at that position would draw -- and the rule above
         holds with "drawn token" for "arg-max".  The accept kernel marks the accepted inputs in the
-        bitmap slots; the uniforms of rejected rows stay stored for their positions."""
+        bitmap slots; the uniforms of rejected rows stay stored for their positions.
+
+        A batch with a guided request (``spec_guided``) takes the sampled form with the sampler's guided
+        verify form: row i of a guided request is masked by the grammar state after the request's text
+        and its draft tokens 1 .. i, which the host walks here and feeds as ``g_in``; the unguided rows
+        ride along with -1.  :meth:`_emit` then walks ``r.gstate`` over the emitted tokens as ever and
+        raises if one is not allowed."""
         T, B = self.spec_T, len(reqs)
-        smp = self._spec_sampled(reqs)
+        gd = self._spec_guided(reqs)
+        smp = gd or self._spec_sampled(reqs)
         ids = np.zeros(B * T, np.int64)
         pos = np.zeros(B * T, np.int32)
         slots = np.full(B * T, -1, np.int64)
@@ -1531,6 +1615,18 @@ class LLMEngine:
             slots[o:o + n] = self.kv.slots(r.rid, r.ctx, n)
         bt = self.kv.block_table([r.rid for r in reqs])
         sample = self._verify_sample_inputs(reqs) if smp else None
+        g_in = None
+        if gd:
+            g_in = np.full(B * T, -1, np.int32)
+            for b, (r, d) in enumerate(zip(reqs, drafts)):
+                g, st = r.params.guide, r.gstate
+                if g is None:
+                    continue
+                for i in range(1 + len(d)):
+                    if i:
+                        st = g.walk(st, d[i - 1])
+                    g_in[b * T + i] = r.guide_base + st
+            sample["g_in"] = g_in
         am = n_acc = None
         if self.graphs is not None and bt.shape[1] <= self.graphs.max_blocks:
             try:
@@ -1544,22 +1640,27 @@ class LLMEngine:
                     for r in reqs:
                         r.seen_n = -1
                     sample = self._verify_sample_inputs(reqs)
+                    if gd:
+                        sample["g_in"] = g_in
         if am is None:
             d = self.device
             logits = self.llm.verify(h2d(ids, d), h2d(pos, d), h2d(slots, d), self.kv, h2d(bt, d), h2d(ctx, d),
                                      h2d(n_rows, d), T, workspace=self._ws)
             if smp:
                 t = lambda k, dt: h2d(sample[k], d, dt)  # noqa: E731
+                # guided: the verify form reads g_in alone; the slot argument of the tensors is not read
                 *_, tok, acc, _seen = lops.sample_verify_rows(
                     logits, T, h2d(n_rows, d), t("inv_t", torch.float32), t("top_p", torch.float64),
                     t("penalty", torch.float32), t("u", torch.float64), t("greedy", torch.int32),
-                    t("seen_slot", torch.int32), self._slots._seen(), h2d(ids, d), candidates=False)
+                    t("seen_slot", torch.int32), self._slots._seen(), h2d(ids, d), candidates=False,
+                    guide=self._arena.tensors(t("g_in", torch.int32), t("g_in", torch.int32)) if gd else None)
                 am, n_acc = tok.cpu().numpy(), acc.cpu().numpy()
             else:
                 _v, i, _lse = ops.row_topk(logits, DecodeGraphs.K_GREEDY, with_lse=True, index_offset=self.llm.v0)
                 am = i[:, 0].cpu().numpy()
         self.stats["spec_steps"] += 1
-        self.stats["spec_sample_steps"] += smp
+        self.stats["spec_sample_steps"] += smp and not gd
+        self.stats["spec_guided_steps"] += gd
         acc = []
         for b, d in enumerate(drafts):
             j = 0
@@ -1575,6 +1676,9 @@ class LLMEngine:
                 r.seen_n = len(r.tokens) + j      # the accept kernel marked tokens[-1] and the accepted draft tokens
             self.stats["spec_drafted"] += len(d)
             self.stats["spec_accepted"] += j
+            if r.draft_forced:
+                self.stats["spec_forced_drafted"] += len(d)
+                self.stats["spec_forced_accepted"] += j
             done = False
             for t in row[:j + 1]:
                 r.ctx += 1

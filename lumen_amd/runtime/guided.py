@@ -592,6 +592,24 @@ def check(kind: str, spec) -> str:
 
 
 # ------------------------------------------------------------------ token tables
+_BYTES_INDEX: dict = {}      # id(token_bytes) -> (token_bytes, {bytes: lowest id}, longest token)
+
+
+def _bytes_index(token_bytes: Sequence[bytes]):
+    """({bytes: the lowest id with these bytes}, length of the longest token) of a vocabulary, built
+    once per vocabulary object (the guides of an engine share one)"""
+    hit = _BYTES_INDEX.get(id(token_bytes))
+    if hit is None or hit[0] is not token_bytes:
+        index: dict = {}
+        for t, b in enumerate(token_bytes):
+            if b:
+                index.setdefault(bytes(b), t)
+        if len(_BYTES_INDEX) >= 8:
+            _BYTES_INDEX.clear()
+        hit = _BYTES_INDEX[id(token_bytes)] = (token_bytes, index, max(map(len, index), default=0))
+    return hit[1], hit[2]
+
+
 class Guide:
     """A compiled grammar over one vocabulary.
 
@@ -607,6 +625,7 @@ class Guide:
         self.token_bytes = token_bytes
         self.eos_ids = frozenset(int(t) for t in eos_ids)
         self.V = len(token_bytes)
+        self._forced: dict = {}      # state -> the tokens of its forced byte run (:meth:`forced`)
 
     @property
     def n_states(self) -> int:
@@ -625,6 +644,41 @@ class Guide:
 
     def allows(self, state: int, token: int) -> bool:
         return 0 <= token < self.V and bool((int(self.allow[state, token >> 5]) >> (token & 31)) & 1)
+
+    def forced(self, state: int, k: int) -> tuple:
+        """At most ``k`` tokens that spell the bytes the grammar forces from ``state``: the DFA is
+        followed while the state is not accepting (there EOS is an alternative) and exactly one byte
+        has a live transition, and that byte run is cut into tokens greedily -- at each point the
+        longest token whose bytes are a prefix of the rest of the run and that the state allows, the
+        lowest id among tokens with equal bytes -- until no whole token fits.  Never EOS, never a
+        token without bytes.  Deterministic and cached per state: the draft of speculative decoding
+        for a guided request (the only way the model can reject it is another tokenisation of the
+        same bytes)."""
+        if k <= 0 or not 0 <= state < self.n_states:
+            return ()
+        hit = self._forced.get(state)
+        if hit is None:
+            run, s = [], state
+            while not self.accept[s] and len(run) < self.n_states:
+                live = np.flatnonzero(self.dfa[s] >= 0)
+                if len(live) != 1:
+                    break
+                run.append(int(live[0]))
+                s = int(self.dfa[s, live[0]])
+            index, longest = _bytes_index(self.token_bytes)
+            run, out, at, s = bytes(run), [], 0, state
+            while at < len(run):
+                for n in range(min(longest, len(run) - at), 0, -1):
+                    t = index.get(run[at:at + n])
+                    if t is not None and t not in self.eos_ids and self.allows(s, t):
+                        break
+                else:
+                    break
+                out.append(t)
+                at += n
+                s = self.walk(s, t)
+            hit = self._forced[state] = tuple(out)
+        return hit[:k]
 
 
 def token_csr(token_bytes: Sequence[bytes]):

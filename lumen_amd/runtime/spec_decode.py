@@ -4,6 +4,11 @@ A drafter is ``callable(token_ids, k) -> list[int]``: given a request's tokens s
 when the caller supplied them, followed by the generated ids) it proposes at most ``k`` tokens that
 may come next.  The engine feeds the proposal through one batched verify step and keeps the prefix
 the model agrees with, so a drafter can only change the speed, never the output.
+
+A guided request (``LUMEN_SPEC_GUIDED``) has a drafter of its own that needs none of these: the
+tokens its grammar forces (:meth:`lumen_amd.runtime.guided.Guide.forced`).  The engine asks the
+drafter here only where the grammar forces nothing, and cuts its proposal at the first token the
+grammar does not allow.
 """
 from __future__ import annotations
 
