@@ -27,7 +27,7 @@ ACTS = {
 }
 
 
-# Held around every hipGraph capture in the process (models/vlm.py, runtime/engine.py):
+# Held around every hipGraph capture in the process (models/vlm.py, runtime/decode_graphs.py):
 # torch.cuda.graph() enters with a device-wide synchronize + empty_cache, which fails (or
 # invalidates) a capture another thread has in progress, thread_local mode or not.
 CAPTURE_LOCK = threading.RLock()

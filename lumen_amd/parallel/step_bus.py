@@ -1,6 +1,6 @@
 """Host shared-memory step bus from TP rank 0 to its follower ranks (``csrc/host/step_bus.cpp``).
 
-:class:`lumen_amd.runtime.engine.TPSync` sends every engine step through it when the whole TP
+:class:`lumen_amd.runtime.tp_sync.TPSync` sends every engine step through it when the whole TP
 group lives on one node (always, for :class:`~lumen_amd.parallel.tp.TPServingGroup`): the
 followers' hosts read the step descriptor straight from shared memory -- no device collective,
 no device->host copy per token -- and launch their decode graphs while the leader launches its

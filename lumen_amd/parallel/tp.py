@@ -1,7 +1,8 @@
 """Tensor-parallel serving group for the VLM decoder.
 
 The gRPC service process is TP rank 0 (the *leader*): it owns the continuous-
-batching engine, tokenizer and sampling, and broadcasts every engine step.
+batching engine, tokenizer and sampling, and broadcasts every engine step
+(:class:`lumen_amd.runtime.tp_sync.TPSync`).
 Ranks 1..N-1 (*followers*) are child processes started here with the torchrun
 environment (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR=127.0.0.1 /
 MASTER_PORT); each builds the same model with its weight shard on its own GPU

@@ -68,8 +68,10 @@ from .. import ops
 from ..ops import llm as lops
 from ..parallel.comm import TPGroupUnavailable
 from ..utils.h2d import h2d, h2d_ahead
+from .decode_graphs import DecodeGraphs, GuideArena, SeenSlots  # noqa: F401 - also imported from here
 from .kv_cache import BLOCK, PagedKVCache
 from .spec_decode import Drafter, NgramDrafter, drafter_from_env, spec_tokens_from_env  # noqa: F401
+from .tp_sync import TPSync, tp_sync_capacity  # noqa: F401 - also imported from here
 
 log = logging.getLogger("lumen.engine")
 
@@ -218,842 +220,6 @@ class Sampler:
         return out
 
 
-class TPSync:
-    """Step channel from rank 0 (the engine) to the follower ranks of a TP group.
-
-    Transport:
-
-    * ``bus`` (default when every rank of the group is on this node -- always, for
-      :class:`~lumen_amd.parallel.tp.TPServingGroup`): a host shared-memory ring
-      (:mod:`lumen_amd.parallel.step_bus`).  A follower's host reads the step straight from shared
-      memory -- no collective and no device->host copy per token -- and launches its step while
-      the leader launches its own.
-    * ``bcast``: ONE broadcast of a 4 KiB prefix of an int32 buffer per step (GPU buffer for RCCL,
-      host for gloo), plus a sized remainder for long descriptors; the follower copies the prefix
-      to the host to parse it.
-
-    A decode step is an 8-int header (op, batch, table width, top-k, flags, message length)
-    followed by the step descriptor -- ids, positions, cache slots, context lengths, block table;
-    nothing is pickled.  ``flags``: 1 = replay the captured graph, 2 = token ids come from the
-    previous replay's in-graph arg-max (look-ahead step), 4 = the graph's in-graph TP sampler is
-    this step's sampler (the follower does nothing after the replay).  Prefill / control messages
-    and decode steps whose sampling needs per-row state (temperatures, repetition-penalty token
-    sets) travel pickled (bus) or as an object broadcast (bcast).
-    ``capacity`` (ints after the header) must hold 4 * batch + batch * table width of the
-    largest decode step: :func:`tp_sync_capacity`.
-    """
-
-    OBJ, DECODE, OBJ_BIG = 1, 2, 3
-    F_GRAPH, F_DEV_IDS, F_INGRAPH = 1, 2, 4
-
-    def __init__(self, group=None, src: int = 0, device: Optional[torch.device] = None, capacity: int = 1 << 15,
-                 transport: Optional[str] = None):
-        import torch.distributed as dist
-
-        self.group, self.src = group, src
-        if device is None:
-            be = dist.get_backend(group) if dist.is_initialized() else "gloo"
-            device = torch.device("cuda", torch.cuda.current_device()) if be == "nccl" else torch.device("cpu")
-        self.device = device
-        self.capacity = int(capacity)
-        self.buf = torch.zeros(8 + self.capacity, dtype=torch.int32, device=device)
-        self.prefix = min(1024, 8 + self.capacity)          # ints per step's first broadcast
-        self.stats = {"tensor_steps": 0, "object_steps": 0, "two_part_steps": 0, "d2h": 0}
-        self.bus = None
-        transport = transport or os.environ.get("LUMEN_TP_STEP_TRANSPORT", "bus")
-        if transport == "bus":
-            self.bus = self._open_bus()
-        self.transport = "bus" if self.bus is not None else "bcast"
-
-    def _open_bus(self):
-        """Collective: a shared-memory bus when all ranks share this host and the host library
-        has it (every rank agrees, else all fall back to broadcasts)."""
-        import socket
-
-        import torch.distributed as dist
-
-        from ..parallel import step_bus
-
-        rank, world = dist.get_rank(self.group), dist.get_world_size(self.group)
-        hosts = [None] * world
-        dist.all_gather_object(hosts, (socket.gethostname(), step_bus.available()), group=self.group)
-        if len({h for h, _ in hosts}) != 1 or not all(ok for _, ok in hosts):
-            return None
-        slot = max(1 << 18, 4 * (8 + self.capacity) + 64)
-        name = [None]
-        bus, err = None, None
-        if rank == self.src:
-            try:
-                name[0] = step_bus.StepBus.unique_name()
-                bus = step_bus.StepBus(name[0], None, nslots=64, slot_bytes=slot, nreaders=world - 1)
-            except Exception as e:  # noqa: BLE001 - agreed fallback below
-                name[0], err = None, e
-        dist.broadcast_object_list(name, src=self.src, group=self.group)
-        if name[0] is not None and rank != self.src:
-            try:
-                bus = step_bus.StepBus(name[0], rank if rank < self.src else rank - 1)
-            except Exception as e:  # noqa: BLE001
-                bus, err = None, e
-        oks = [None] * world
-        dist.all_gather_object(oks, bus is not None, group=self.group)
-        if rank == self.src and bus is not None:
-            bus.unlink()                       # every rank holds its mapping (or gave up): drop the name
-        if not all(oks):
-            if bus is not None:
-                bus.close()
-            log.warning("TP step bus unavailable (%s); stepping over broadcasts", err)
-            return None
-        return bus
-
-    def _bcast(self, t: torch.Tensor) -> None:
-        import torch.distributed as dist
-
-        dist.broadcast(t, src=self.src, group=self.group)
-
-    def send(self, msg) -> None:
-        import pickle
-
-        import torch.distributed as dist
-
-        self.stats["object_steps"] += 1
-        if self.bus is not None:
-            data = pickle.dumps(msg, protocol=pickle.HIGHEST_PROTOCOL)
-            head = np.zeros(8, np.int32)
-            if 32 + len(data) <= self.bus.slot_bytes:
-                head[0] = self.OBJ
-                self.bus.publish(head.tobytes() + data)
-                return
-            head[0] = self.OBJ_BIG
-            self.bus.publish(head)
-        else:
-            self.buf[:8].fill_(0)
-            self.buf[0] = self.OBJ
-            self._bcast(self.buf[:self.prefix])
-        dist.broadcast_object_list([msg], src=self.src, group=self.group)
-
-    def send_decode(self, ids, pos, slots, bt, ctx, spec, graph: bool, ingraph: bool = False) -> None:
-        """``ids`` None: the previous replay's in-graph arg-max feeds this step (look-ahead)."""
-        B, W = len(pos), bt.shape[1]
-        if spec["inv"] is not None or spec["pen"] is not None or 4 * B + B * W > self.capacity:
-            self.send(("decode", ids, pos, slots, bt, ctx, spec, graph, ingraph))
-            return
-        n = 8 + 4 * B + B * W
-        flags = (self.F_GRAPH if graph else 0) | (self.F_DEV_IDS if ids is None else 0) | \
-            (self.F_INGRAPH if ingraph else 0)
-        msg = np.zeros(n, np.int32)
-        msg[:8] = [self.DECODE, B, W, spec["k"], flags, n, 0, 0]
-        if ids is not None:
-            msg[8:8 + B] = np.asarray(ids, np.int64).astype(np.int32)
-        msg[8 + B:] = np.concatenate([np.asarray(pos, np.int32), np.asarray(slots, np.int64).astype(np.int32),
-                                      np.asarray(ctx, np.int32), np.asarray(bt, np.int32).reshape(-1)])
-        self.stats["tensor_steps"] += 1
-        if self.bus is not None:
-            self.bus.publish(msg)
-            return
-        self.buf[:n].copy_(torch.from_numpy(msg), non_blocking=self.device.type == "cuda")
-        self._bcast(self.buf[:self.prefix])
-        if n > self.prefix:
-            self._bcast(self.buf[self.prefix:n])
-            self.stats["two_part_steps"] += 1
-
-    def _parse_decode(self, p: np.ndarray):
-        h = p[:8].tolist()
-        B, W, k, flags = h[1], h[2], h[3], h[4]
-        p = p[8:8 + 4 * B + B * W]
-        ids = None if flags & self.F_DEV_IDS else p[:B].astype(np.int64)
-        pos = p[B:2 * B].copy()
-        slots = p[2 * B:3 * B].astype(np.int64)
-        ctx = p[3 * B:4 * B].copy()
-        bt = p[4 * B:].reshape(B, W).copy()
-        return ("decode", ids, pos, slots, bt, ctx, {"k": k, "inv": None, "pen": None, "pen_ids": None},
-                bool(flags & self.F_GRAPH), bool(flags & self.F_INGRAPH))
-
-    def _recv_obj(self):
-        import torch.distributed as dist
-
-        obj = [None]
-        dist.broadcast_object_list(obj, src=self.src, group=self.group)
-        return obj[0]
-
-    def recv(self):
-        if self.bus is not None:
-            import pickle
-
-            from ..parallel.step_bus import BusClosed
-
-            while True:
-                try:
-                    m = self.bus.next(timeout_ms=1000)
-                except BusClosed:
-                    return ("stop",)
-                if m is not None:
-                    break
-                if not self.bus.writer_alive():
-                    return ("stop",)
-            op = int(np.frombuffer(m[:4], np.int32)[0])
-            if op == self.OBJ:
-                return pickle.loads(m[32:])     # written by this group's own leader process
-            if op == self.OBJ_BIG:
-                return self._recv_obj()
-            return self._parse_decode(np.frombuffer(m, np.int32))
-        self._bcast(self.buf[:self.prefix])
-        p = self.buf[:self.prefix].cpu().numpy()
-        self.stats["d2h"] += 1
-        if int(p[0]) == self.OBJ:
-            return self._recv_obj()
-        n = int(p[5])
-        if n > self.prefix:
-            self._bcast(self.buf[self.prefix:n])
-            p = self.buf[:n].cpu().numpy()
-            self.stats["d2h"] += 1
-        return self._parse_decode(p)
-
-    def close(self) -> None:
-        if self.bus is not None:
-            self.bus.close()
-            self.bus = None
-
-
-def tp_sync_capacity(max_batch: int, max_position: int) -> int:
-    """Descriptor ints of the largest decode step: 4 per row + the block table (64-token blocks)."""
-    return max_batch * (4 + -(-max_position // 64))
-
-
-class SeenSlots:
-    """The device sampler's seen-token bitmaps: [max_batch, ceil(V / 32)] int32 (19 KB per row at
-    V = 151,936), one row = "slot" per penalised request, allocated on first use.  :class:`DecodeGraphs`
-    is one; an engine without graphs that samples verify steps holds a bare one."""
-
-    def __init__(self, llm, max_batch: int):
-        self.llm = llm
-        self.max_batch = max(max_batch, 1)
-        self.seen: Optional[torch.Tensor] = None
-        self._free_slots = list(range(self.max_batch - 1, -1, -1))
-
-    def _seen(self) -> torch.Tensor:
-        if self.seen is None:
-            self.seen = torch.zeros((self.max_batch, lops.seen_words(self.llm.Vl)), dtype=torch.int32,
-                                    device=self.llm.embed.device)
-        return self.seen
-
-    def take_slot(self) -> Optional[int]:
-        """a free row of the seen bitmap (None: all taken); fill it with :meth:`write_slot`"""
-        return self._free_slots.pop() if self._free_slots else None
-
-    def free_slot(self, slot: int) -> None:
-        self._free_slots.append(slot)
-
-    def write_slot(self, slot: int, tokens: Sequence[int]) -> None:
-        """Set row ``slot`` of the bitmap to exactly ``tokens`` (none: zero it), on the current
-        stream -- the one the graphs replay on, so it lands after every step launched before."""
-        seen = self._seen()
-        row = np.zeros(seen.shape[1], np.uint32)
-        t = np.asarray([x for x in tokens if 0 <= x < self.llm.Vl], np.int64)
-        if len(t):
-            np.bitwise_or.at(row, t >> 5, np.uint32(1) << (t & 31).astype(np.uint32))
-        seen[slot].copy_(torch.from_numpy(row.view(np.int32)))
-
-
-class GuideArena:
-    """The device side of guided decoding: ``LUMEN_GUIDED_STATES`` rows (default 4096; 19 KB each
-    at V = 151,936) of allowed-token bitmaps and of byte transitions in arena-global state ids, the
-    CSR of the token bytes (one copy per engine) and one grammar state per running sequence.
-
-    Allocated once, before the first ``guided`` graph is captured, so the pointers the graphs hold
-    stay valid.  A guide is uploaded on first use into a free run of rows and stays resident; when
-    a new one does not fit, the least recently used guides that no running request refers to are
-    evicted.  A guide that cannot fit raises :class:`~lumen_amd.runtime.guided.GuideError`, which
-    fails that request only."""
-
-    def __init__(self, llm, max_batch: int, token_bytes: Sequence[bytes], rows: Optional[int] = None):
-        from .guided import token_csr
-
-        d = llm.embed.device
-        self.V = llm.Vl
-        self.rows = int(rows or os.environ.get("LUMEN_GUIDED_STATES", 4096))
-        if not 1 <= self.rows <= 32767:
-            raise ValueError("LUMEN_GUIDED_STATES: 1 .. 32767 (arena-global state ids are int16)")
-        self.words = lops.seen_words(self.V)
-        self.allow = torch.zeros((self.rows, self.words), dtype=torch.int32, device=d)
-        self.dfa = torch.full((self.rows, 256), -1, dtype=torch.int16, device=d)
-        self.token_bytes = token_bytes
-        tb = list(token_bytes[:self.V]) + [b""] * max(0, self.V - len(token_bytes))
-        off, dat = token_csr(tb)
-        self.tok_off = torch.from_numpy(off).to(d)
-        self.tok_dat = torch.from_numpy(dat.copy()).to(d)
-        self.state = torch.zeros(max(max_batch, 1), dtype=torch.int32, device=d)
-        self._free_slots = list(range(max(max_batch, 1) - 1, -1, -1))
-        self._res: "dict[int, dict]" = {}      # id(guide) -> {"g", "base", "n", "refs"}, least recently used first
-
-    def take_slot(self) -> Optional[int]:
-        return self._free_slots.pop() if self._free_slots else None
-
-    def free_slot(self, slot: int) -> None:
-        self._free_slots.append(slot)
-
-    def _gap(self, n: int) -> Optional[int]:
-        """first row of a free run of ``n`` rows (first fit), or None"""
-        at = 0
-        for e in sorted(self._res.values(), key=lambda e: e["base"]):
-            if e["base"] - at >= n:
-                return at
-            at = e["base"] + e["n"]
-        return at if self.rows - at >= n else None
-
-    def acquire(self, g) -> int:
-        """first arena row of guide ``g``, uploading it if it is not resident; takes a reference"""
-        from .guided import GuideError
-
-        e = self._res.pop(id(g), None)
-        if e is None:
-            n = g.n_states
-            if g.token_bytes is not self.token_bytes and list(g.token_bytes) != list(self.token_bytes):
-                raise GuideError("the guide was compiled for another vocabulary than this engine's guides")
-            if n > self.rows or g.V > self.V:
-                raise GuideError(f"a guide of {n} states over {g.V} tokens does not fit the arena "
-                                 f"(LUMEN_GUIDED_STATES = {self.rows}, vocabulary {self.V})")
-            base = self._gap(n)
-            while base is None:
-                idle = next((k for k, v in self._res.items() if v["refs"] == 0), None)
-                if idle is None:
-                    raise GuideError(f"no room for a guide of {n} states: the arena's {self.rows} rows "
-                                     "(LUMEN_GUIDED_STATES) are held by the guides of running requests")
-                del self._res[idle]
-                base = self._gap(n)
-            # on the current stream, the one the graphs replay on: after every step launched before
-            rows = np.zeros((n, self.words), np.int32)
-            rows[:, :g.allow.shape[1]] = g.allow
-            self.allow[base:base + n].copy_(torch.from_numpy(rows))
-            dfa = np.where(g.dfa >= 0, g.dfa.astype(np.int32) + base, -1).astype(np.int16)
-            self.dfa[base:base + n].copy_(torch.from_numpy(dfa))
-            e = {"g": g, "base": base, "n": n, "refs": 0}
-        e["refs"] += 1
-        self._res[id(g)] = e                   # most recently used last
-        return e["base"]
-
-    def release(self, g) -> None:
-        e = self._res.get(id(g))
-        if e is not None and e["refs"] > 0:
-            e["refs"] -= 1
-
-    def tensors(self, g_slot: torch.Tensor, g_in: torch.Tensor):
-        return lops.GuideTensors(self.allow, self.dfa, self.tok_off, self.tok_dat, g_slot, g_in, self.state)
-
-
-class DecodeGraphs(SeenSlots):
-    """hipGraph-captured decode steps, one graph per (padded batch-size, table-width) bucket.
-
-    A decode step is ~5 kernels per layer (hundreds per token) whose host launch cost
-    dominates small-batch decode; replaying a captured graph issues them in one call.
-    Inputs live in ONE device buffer per graph (positions, context lengths, block table of
-    fixed width, cache slots) filled by ONE H2D copy from a pinned staging buffer; padded
-    rows use slot -1 (no cache write) and context 1, and their logits are ignored.
-
-    The graph also holds the greedy sampler: the row top-8 candidates + row lse go to one
-    packed result buffer (one D2H per step) and the arg-max token is written straight into the
-    batch bucket's token-id buffer, which every graph of that bucket embeds from -- so the NEXT
-    step can be launched before the host has read this one (:meth:`launch` with ``ids=None``;
-    LLMEngine's look-ahead decode).  Under TP the vocab-parallel merge is captured too: each
-    rank's shard top-8 + lse go into its row of a [world, B, 20] fp32 block, ONE all-reduce
-    (the IPC one-shot kernel) gives every rank every shard's candidates, and the global top-8,
-    the lse of the shard lse's and the arg-max are computed on every rank identically -- so the
-    followers never read anything back and look-ahead works under TP.  The last word of the
-    result buffer is the IPC all-reduce error flag, copied after the step's last all-reduce:
-    the leader sees it in the same D2H as the tokens, before emitting them.  Staging and result
-    buffers are double-buffered and fenced by the event of the launch that last used them.
-
-    ``mode="sample"`` graphs (single GPU, captured on first need; the greedy graphs, their step
-    buffer and their result buffer are untouched by them) end in the device sampler
-    (``sample_rows``, csrc/sampler.hip) instead of the top-8 + arg-max: repetition penalty over a
-    per-request bitmap of the tokens fed so far (``seen``, one row = "slot" per penalised
-    request), temperature, top-64 candidates, nucleus cut and the draw with a uniform the host
-    supplies, so sampled and penalised requests replay and look ahead like greedy ones.  Their step
-    buffer also carries per-row 1/T, top_p, penalty, greedy flag, bitmap slot and uniform; their
-    result buffer is the tokens plus the error word.  Padded rows are greedy with slot -1.
-
-    ``mode="verify"`` graphs (speculative decoding, single GPU; again with buffers of their own)
-    run :meth:`LLM.verify` over T rows per sequence, at most 32 rows in all: the step buffer carries
-    token ids, positions and slots of Bp * T rows and context length, live-row count and block
-    table of Bp sequences; the result buffer is the arg-max token of every row plus the error
-    word.  Padded rows use slot -1; padded sequences context 1 with one live row.
-
-    ``mode="verify_sample"`` graphs are the verify step with the device sampler's verify form
-    (``sample_verify_rows``: the draw of every row, then ``verify_accept``) in place of the row
-    arg-max, for batches with sampled or penalised requests.  The step buffer also carries the
-    sampler's per-sequence rows (as in ``sample`` mode) and one uniform per row; the result buffer is
-    the drawn token of every row, the accepted draft tokens of every sequence and the error word.
-    Padded sequences are greedy with slot -1 and one live row.
-
-    ``mode="verify_guided"`` graphs are the ``verify_sample`` graphs with the sampler's guided verify
-    form, for batches with a guided request (speculative decoding of guided requests): the step
-    buffer also carries ``g_in`` of Bp * T rows, the arena-global grammar state in which each row
-    draws (-1 for an unguided, dead or padded row).  No state is kept on the device between verify
-    steps.  They need :attr:`arena` like the ``guided`` graphs.
-
-    ``mode="guided"`` graphs are the ``sample`` graphs with the sampler's guided form: the step
-    buffer also carries per row the sequence's row of the device's grammar states (``g_slot``, -1
-    for an unguided or padded row) and the state the host feeds (``g_in``, -1 on a look-ahead step,
-    which reads the state the step before it stored).  They need :attr:`arena` (a
-    :class:`GuideArena`), set before the first of them is captured.
-    """
-
-    BUCKETS = (1, 2, 4, 8, 16, 32, 64, 128)
-    K_GREEDY = 8
-
-    def __init__(self, llm, kv: PagedKVCache, max_batch: int, max_blocks: int):
-        SeenSlots.__init__(self, llm, max_batch)     # sample / verify_sample modes: the seen-token bitmaps
-        self.kv = kv
-        self.max_blocks = max_blocks
-        self.buckets = [b for b in self.BUCKETS if b <= max(max_batch, 1)] or [1]
-        if self.buckets[-1] < max_batch:
-            self.buckets.append(max_batch)
-        self.graphs: dict[tuple, dict] = {}
-        self.ids: dict[int, torch.Tensor] = {}       # batch bucket -> device token ids (shared by its graphs)
-        self.pool = None
-        self.in_graph_sampler = not llm.tp.enabled or os.environ.get("LUMEN_TP_INGRAPH_SAMPLER", "1") == "1"
-        self._stream = None     # the capture stream, private to this instance (see _capture_stream)
-        self.arena: Optional[GuideArena] = None      # guided mode: set by the engine before its first capture
-
-    def _bucket(self, B: int) -> int:
-        for b in self.buckets:
-            if b >= B:
-                return b
-        raise ValueError(f"batch {B} exceeds graph buckets {self.buckets}")
-
-    def _width(self, w: int) -> int:
-        """block-table width bucket: the decode kernel's split count follows the width,
-        so short contexts must not pay for the maximum-length table."""
-        for b in (8, 32, 128):
-            if w <= b and b <= self.max_blocks:
-                return b
-        return self.max_blocks
-
-    @staticmethod
-    def _layout(Bp: int, W: int) -> dict:
-        """byte offsets of (slots i64, pos i32, ctx i32, bt i32) in the step buffer"""
-        o_pos = 8 * Bp
-        o_ctx = o_pos + 4 * Bp
-        o_bt = o_ctx + 4 * Bp
-        return {"slots": (0, Bp), "pos": (o_pos, Bp), "ctx": (o_ctx, Bp), "bt": (o_bt, Bp * W),
-                "bytes": -(-(o_bt + 4 * Bp * W) // 16) * 16}
-
-    @staticmethod
-    def _layout_sample(Bp: int, W: int) -> dict:
-        """the greedy layout followed by the sampler's rows: (u f64, top_p f64, inv_t f32, penalty
-        f32, greedy i32, seen_slot i32); the f64 rows start 16-byte aligned"""
-        lay = dict(DecodeGraphs._layout(Bp, W))
-        o = lay["bytes"]
-        for k, sz in (("u", 8), ("top_p", 8), ("inv_t", 4), ("penalty", 4), ("greedy", 4), ("seen_slot", 4)):
-            lay[k] = (o, Bp)
-            o += sz * Bp
-        lay["bytes"] = -(-o // 16) * 16
-        return lay
-
-    _SAMPLE_ROWS = {"u": torch.float64, "top_p": torch.float64, "inv_t": torch.float32, "penalty": torch.float32,
-                    "greedy": torch.int32, "seen_slot": torch.int32}
-    _SAMPLE_PAD = {"u": 0.0, "top_p": 1.0, "inv_t": 1.0, "penalty": 1.0, "greedy": 1, "seen_slot": -1}
-    _GUIDE_ROWS = {"g_slot": torch.int32, "g_in": torch.int32}      # guided mode, after the sampler's rows
-    _GUIDE_PAD = {"g_slot": -1, "g_in": -1}
-
-    @staticmethod
-    def _layout_guided(Bp: int, W: int) -> dict:
-        """the sample layout followed by (g_slot i32, g_in i32)"""
-        lay = dict(DecodeGraphs._layout_sample(Bp, W))
-        o = lay["bytes"]
-        for k in DecodeGraphs._GUIDE_ROWS:
-            lay[k] = (o, Bp)
-            o += 4 * Bp
-        lay["bytes"] = -(-o // 16) * 16
-        return lay
-
-    def _capture_stream(self, d: torch.device) -> torch.cuda.Stream:
-        """One stream per engine that nothing else ever uses.  The split-K tickets and
-        workspaces the kernels key by stream are baked into the graphs captured on it; a
-        stream from PyTorch's recycled pool could later be handed to another thread's eager
-        split-K work while a graph replays, and the two would share counters."""
-        if self._stream is None:
-            self._stream = ops.private_stream(d)
-        return self._stream
-
-    def _record(self, run, d: torch.device):
-        """Warm ``run`` up twice on the private stream, then capture it; returns (graph, run's result)."""
-        s = self._capture_stream(d)
-        s.wait_stream(torch.cuda.current_stream(d))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                run()
-        torch.cuda.current_stream(d).wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        if self.pool is None:
-            self.pool = torch.cuda.graph_pool_handle()
-        # captured on the warm-up stream: the split-K tickets / workspaces the kernels key by stream
-        # already exist (a first request inside the capture would record its zero-fill into every replay)
-        # thread_local: a multi-service engine process runs other services' batch loops on other
-        # threads meanwhile; the default (global) mode would fail their HIP calls during the capture
-        # (ops.CAPTURE_LOCK: one capture at a time in the process, see there)
-        with ops.CAPTURE_LOCK, torch.cuda.graph(g, pool=self.pool, stream=s, capture_error_mode="thread_local"):
-            out = run()
-        return g, out
-
-    def _capture(self, Bp: int, W: int, mode: str = "greedy") -> dict:
-        d = self.llm.embed.device
-        guided = mode == "guided"
-        sample = mode == "sample" or guided
-        if guided and self.arena is None:
-            raise RuntimeError("guided graphs need the guide arena")
-        lay = self._layout_guided(Bp, W) if guided else self._layout_sample(Bp, W) if sample else self._layout(Bp, W)
-        dbuf = torch.zeros(lay["bytes"], dtype=torch.uint8, device=d)
-
-        def views(buf):
-            o, n = lay["slots"]
-            v = {"slots": buf[o:o + 8 * n].view(torch.int64)}
-            for k in ("pos", "ctx"):
-                o, n = lay[k]
-                v[k] = buf[o:o + 4 * n].view(torch.int32)
-            o, n = lay["bt"]
-            v["bt"] = buf[o:o + 4 * n].view(torch.int32).view(Bp, W)
-            if sample:
-                for k, dt in self._SAMPLE_ROWS.items():
-                    o, n = lay[k]
-                    v[k] = buf[o:o + dt.itemsize * n].view(dt)
-            if guided:
-                for k, dt in self._GUIDE_ROWS.items():
-                    o, n = lay[k]
-                    v[k] = buf[o:o + dt.itemsize * n].view(dt)
-            return v
-
-        st = views(dbuf)
-        st["slots"].fill_(-1)
-        st["ctx"].fill_(1)
-        if sample:
-            for k, pad in self._SAMPLE_PAD.items():
-                st[k].fill_(pad)
-        if guided:
-            for k, pad in self._GUIDE_PAD.items():
-                st[k].fill_(pad)
-            ar = self.arena
-        if Bp not in self.ids:
-            self.ids[Bp] = torch.zeros(Bp, dtype=torch.long, device=d)
-        ids = self.ids[Bp]
-        k = self.K_GREEDY
-        res = torch.zeros(2 * Bp * k + Bp + 1, dtype=torch.float32, device=d) if self.in_graph_sampler else None
-        if sample:
-            res = torch.zeros(Bp + 1, dtype=torch.int32, device=d)      # tokens + the error word
-            seen = self._seen()
-        tp = self.llm.tp
-        KP = 2 * k + 4                      # per-row candidate record: k values, k ids, lse, pad to 16 B
-        gat = torch.zeros((tp.world, Bp, KP), dtype=torch.float32, device=d) if res is not None and tp.enabled \
-            else None
-        loc = torch.zeros(2 * Bp * k + Bp, dtype=torch.float32, device=d) if gat is not None else None
-        ws: dict = {}
-
-        def run():
-            logits = self.llm.decode(ids, st["pos"], st["slots"], self.kv, st["bt"], st["ctx"], workspace=ws)
-            if guided:
-                # the sample call below with the guided form's tensors: masks by the row's grammar state
-                # (st["g_in"], or the arena's state array on a look-ahead step) and stores the new state
-                ops.hip_ops().sample_rows(logits, st["inv_t"], st["top_p"], st["penalty"], st["u"], st["greedy"],
-                                          st["seen_slot"], seen, ids, ids, res[:Bp], None, None, None,
-                                          ar.allow, ar.dfa, ar.tok_off, ar.tok_dat, st["g_slot"], st["g_in"],
-                                          ar.state)
-            elif sample:
-                # reads ids (the step's input tokens: penalised and marked) and writes the drawn ones back
-                ops.hip_ops().sample_rows(logits, st["inv_t"], st["top_p"], st["penalty"], st["u"], st["greedy"],
-                                          st["seen_slot"], seen, ids, ids, res[:Bp], None, None, None)
-            elif res is not None:
-                v = res[:Bp * k].view(Bp, k)
-                i = res[Bp * k:2 * Bp * k].view(torch.int32).view(Bp, k)
-                lse = res[2 * Bp * k:2 * Bp * k + Bp]
-                hip = ops.hip_ops()
-                if gat is None:
-                    hip.row_topk(logits, k, 1.0, v, i, lse, int(self.llm.v0))
-                else:
-                    lv = loc[:Bp * k].view(Bp, k)
-                    li = loc[Bp * k:2 * Bp * k].view(torch.int32).view(Bp, k)
-                    hip.row_topk(logits, k, 1.0, lv, li, loc[2 * Bp * k:], int(self.llm.v0))
-                    gat.zero_()
-                    own = gat[tp.rank]
-                    own[:, :k].copy_(lv)
-                    own[:, k:2 * k].copy_(li)                 # global vocab ids < 2^24: exact in fp32
-                    own[:, 2 * k].copy_(loc[2 * Bp * k:])
-                    self.llm._all_reduce(gat)
-                    vals = gat[:, :, :k].permute(1, 0, 2).reshape(Bp, tp.world * k)
-                    gids = gat[:, :, k:2 * k].permute(1, 0, 2).reshape(Bp, tp.world * k)
-                    tv, order = torch.topk(vals, k, dim=1)
-                    v.copy_(tv)
-                    i.copy_(torch.gather(gids, 1, order))
-                    lse.copy_(torch.logsumexp(gat[:, :, 2 * k], 0))
-                    comm = getattr(self.llm, "comm", None)
-                    if comm is not None:
-                        comm.error_into(res[2 * Bp * k + Bp:].view(torch.int32))
-                ids.copy_(i[:, 0])                                   # greedy next token, on the device
-            return logits
-
-        g, out = self._record(run, d)
-        pin = lambda t: torch.empty(t.shape, dtype=t.dtype).pin_memory()  # noqa: E731
-        ent = {"g": g, "st": st, "dbuf": dbuf, "out": out, "ws": ws, "res": res, "lay": lay, "Bp": Bp, "W": W,
-               "h_step": [pin(dbuf) for _ in range(2)], "h_ids": [pin(ids) for _ in range(2)],
-               "h_res": [pin(res) for _ in range(2)] if res is not None else None,
-               "ev": [None, None], "par": 0, "mode": mode}
-        ent["h_views"] = [views(h) for h in ent["h_step"]]
-        self.graphs[(Bp, W, mode)] = ent
-        return ent
-
-    def _entry(self, B: int, width: int, mode: str = "greedy") -> dict:
-        key = (self._bucket(B), self._width(width), mode)
-        return self.graphs[key] if key in self.graphs else self._capture(*key)
-
-    def launch(self, ids, pos, slots, bt, ctx, fetch: bool = True, sample: Optional[dict] = None) -> dict:
-        """Stage + replay one step (host arrays; ``ids=None``: the token ids the previous
-        replay of this batch bucket wrote on the device).  Returns a handle for
-        :meth:`tokens` / :meth:`logits`.  ``fetch=False`` (TP followers): no result copy.
-        ``sample``: per-row arrays of the device sampler (keys of ``_SAMPLE_ROWS``) -- the step
-        runs the ``sample`` graph and :meth:`sampled` reads its tokens; with the keys of
-        ``_GUIDE_ROWS`` too, the ``guided`` graph."""
-        B = len(pos)
-        guided = sample is not None and "g_slot" in sample
-        e = self._entry(B, bt.shape[1], "greedy" if sample is None else "guided" if guided else "sample")
-        Bp, W = e["Bp"], e["W"]
-        par = e["par"]
-        e["par"] ^= 1
-        if e["ev"][par] is not None:
-            e["ev"][par].synchronize()        # the copies that last used these pinned buffers are done
-        hv = e["h_views"][par]
-        w = min(bt.shape[1], W)
-        sl, po, cx, tb = (hv[k].numpy() for k in ("slots", "pos", "ctx", "bt"))
-        sl[:] = -1
-        sl[:B] = slots
-        po[:] = 0
-        po[:B] = pos
-        cx[:] = 1
-        cx[:B] = ctx
-        tb[:] = 0
-        tb[:B, :w] = bt[:, :w]
-        if sample is not None:
-            for k, pad in self._SAMPLE_PAD.items():
-                a = hv[k].numpy()
-                a[:] = pad
-                a[:B] = sample[k]
-            if guided:
-                for k, pad in self._GUIDE_PAD.items():
-                    a = hv[k].numpy()
-                    a[:] = pad
-                    a[:B] = sample[k]
-        e["dbuf"].copy_(e["h_step"][par], non_blocking=True)
-        if ids is not None:
-            hi = e["h_ids"][par].numpy()
-            hi[:] = 0
-            hi[:B] = ids
-            self.ids[Bp].copy_(e["h_ids"][par], non_blocking=True)
-        e["g"].replay()
-        if e["res"] is not None and fetch:
-            e["h_res"][par].copy_(e["res"], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        e["ev"][par] = ev
-        return {"e": e, "par": par, "B": B, "ev": ev}
-
-    def tokens(self, h: dict):
-        """(values [B, 8], ids [B, 8], lse [B]) numpy of a launched step (waits for it); sets
-        ``h["err"]`` from the step's all-reduce error word (TP)."""
-        e, B = h["e"], h["B"]
-        h["ev"].synchronize()
-        r = e["h_res"][h["par"]]
-        Bp, k = e["Bp"], self.K_GREEDY
-        h["err"] = int(r[2 * Bp * k + Bp:].view(torch.int32)[0])
-        v = r[:Bp * k].view(Bp, k)[:B].numpy()
-        i = r[Bp * k:2 * Bp * k].view(torch.int32).view(Bp, k)[:B].numpy()
-        return v, i, r[2 * Bp * k:2 * Bp * k + B].numpy()
-
-    def sampled(self, h: dict) -> np.ndarray:
-        """tokens [B] int32 of a launched ``sample`` step (waits for it); sets ``h["err"]``"""
-        e, B = h["e"], h["B"]
-        h["ev"].synchronize()
-        r = e["h_res"][h["par"]].numpy()
-        h["err"] = int(r[e["Bp"]])
-        return r[:B]
-
-    # ---- verify mode (speculative decoding): up to T rows per sequence, single GPU
-    def verify_bucket(self, B: int, T: int) -> int:
-        """padded sequence count of a verify step: the batch bucket while its rows fit the 32-row
-        decode GEMMs, else the largest count that does"""
-        Bp = self._bucket(B)
-        return Bp if Bp * T <= 32 else 32 // T
-
-    @staticmethod
-    def _layout_verify(Bp: int, W: int, T: int) -> dict:
-        """byte offsets of (slots i64, ids i64, pos i32: Bp * T rows; ctx, n_rows, bt i32: Bp sequences)"""
-        R = Bp * T
-        o_ids = 8 * R
-        o_pos = o_ids + 8 * R
-        o_ctx = o_pos + 4 * R
-        o_n = o_ctx + 4 * Bp
-        o_bt = o_n + 4 * Bp
-        return {"slots": (0, R), "ids": (o_ids, R), "pos": (o_pos, R), "ctx": (o_ctx, Bp), "n_rows": (o_n, Bp),
-                "bt": (o_bt, Bp * W), "bytes": -(-(o_bt + 4 * Bp * W) // 16) * 16}
-
-    @staticmethod
-    def _layout_verify_sample(Bp: int, W: int, T: int) -> dict:
-        """the verify layout followed by the sampler's rows: u f64 of Bp * T rows, then (top_p f64,
-        inv_t f32, penalty f32, greedy i32, seen_slot i32) of Bp sequences; the f64 rows start
-        16-byte aligned"""
-        lay = dict(DecodeGraphs._layout_verify(Bp, W, T))
-        o = lay["bytes"]
-        for k, sz, n in (("u", 8, Bp * T), ("top_p", 8, Bp), ("inv_t", 4, Bp), ("penalty", 4, Bp), ("greedy", 4, Bp),
-                         ("seen_slot", 4, Bp)):
-            lay[k] = (o, n)
-            o += sz * n
-        lay["bytes"] = -(-o // 16) * 16
-        return lay
-
-    @staticmethod
-    def _layout_verify_guided(Bp: int, W: int, T: int) -> dict:
-        """the verify_sample layout followed by g_in i32 of Bp * T rows"""
-        lay = dict(DecodeGraphs._layout_verify_sample(Bp, W, T))
-        lay["g_in"] = (lay["bytes"], Bp * T)
-        lay["bytes"] = -(-(lay["bytes"] + 4 * Bp * T) // 16) * 16
-        return lay
-
-    def _capture_verify(self, Bp: int, W: int, T: int, sample: bool = False, guided: bool = False) -> dict:
-        """``sample``: the ``verify_sample`` graph -- the device sampler's verify form and its accept
-        kernel in place of the row arg-max; ``res`` = tok [Bp * T], n_acc [Bp] and the error word.
-        ``guided``: the ``verify_guided`` graph -- the same with the sampler's guided verify form"""
-        d = self.llm.embed.device
-        sample = sample or guided
-        if guided and self.arena is None:
-            raise RuntimeError("guided graphs need the guide arena")
-        lay = self._layout_verify_guided(Bp, W, T) if guided else self._layout_verify_sample(Bp, W, T) if sample \
-            else self._layout_verify(Bp, W, T)
-        R, k = Bp * T, self.K_GREEDY
-        dbuf = torch.zeros(lay["bytes"], dtype=torch.uint8, device=d)
-
-        def views(buf):
-            v = {}
-            for name, dt in (("slots", torch.int64), ("ids", torch.int64), ("pos", torch.int32),
-                             ("ctx", torch.int32), ("n_rows", torch.int32), ("bt", torch.int32)):
-                o, n = lay[name]
-                v[name] = buf[o:o + dt.itemsize * n].view(dt)
-            v["bt"] = v["bt"].view(Bp, W)
-            if sample:
-                for name, dt in self._SAMPLE_ROWS.items():
-                    o, n = lay[name]
-                    v[name] = buf[o:o + dt.itemsize * n].view(dt)
-            if guided:
-                o, n = lay["g_in"]
-                v["g_in"] = buf[o:o + 4 * n].view(torch.int32)
-            return v
-
-        st = views(dbuf)
-        st["slots"].fill_(-1)
-        st["ctx"].fill_(1)
-        st["n_rows"].fill_(1)
-        ws: dict = {}
-        if sample:
-            for name, pad in self._SAMPLE_PAD.items():
-                st[name].fill_(pad)
-            res = torch.zeros(R + Bp + 1, dtype=torch.int32, device=d)
-            seen = self._seen()
-            gargs = ()
-            if guided:
-                st["g_in"].fill_(-1)
-                ar = self.arena
-                # the guided verify form reads the arena's allow rows and g_in; the slot argument is not read
-                gargs = (ar.allow, ar.dfa, ar.tok_off, ar.tok_dat, st["g_in"], st["g_in"], ar.state)
-
-            def run():
-                logits = self.llm.verify(st["ids"], st["pos"], st["slots"], self.kv, st["bt"], st["ctx"], st["n_rows"],
-                                         T, workspace=ws)
-                ops.hip_ops().sample_verify_rows(logits, T, st["n_rows"], st["inv_t"], st["top_p"], st["penalty"],
-                                                 st["u"], st["greedy"], st["seen_slot"], seen, st["ids"], res[:R],
-                                                 res[R:R + Bp], None, None, None, *gargs)
-                return logits
-        else:
-            res = torch.zeros(R + 1, dtype=torch.int32, device=d)          # arg-max token per row + the error word
-            cand = torch.zeros(2 * R * k + R, dtype=torch.float32, device=d)
-
-            def run():
-                logits = self.llm.verify(st["ids"], st["pos"], st["slots"], self.kv, st["bt"], st["ctx"], st["n_rows"],
-                                         T, workspace=ws)
-                i = cand[R * k:2 * R * k].view(torch.int32).view(R, k)
-                ops.hip_ops().row_topk(logits, k, 1.0, cand[:R * k].view(R, k), i, cand[2 * R * k:], int(self.llm.v0))
-                res[:R].copy_(i[:, 0])
-                return logits
-
-        g, out = self._record(run, d)
-        pin = lambda t: torch.empty(t.shape, dtype=t.dtype).pin_memory()  # noqa: E731
-        mode = "verify_guided" if guided else "verify_sample" if sample else "verify"
-        ent = {"g": g, "st": st, "dbuf": dbuf, "out": out, "ws": ws, "res": res, "lay": lay, "Bp": Bp, "W": W, "T": T,
-               "h_step": [pin(dbuf) for _ in range(2)], "h_res": [pin(res) for _ in range(2)],
-               "ev": [None, None], "par": 0, "mode": mode}
-        ent["h_views"] = [views(h) for h in ent["h_step"]]
-        self.graphs[(Bp, W, mode)] = ent
-        return ent
-
-    def _entry_verify(self, B: int, width: int, T: int, sample: bool = False, guided: bool = False) -> dict:
-        key = (self.verify_bucket(B, T), self._width(width),
-               "verify_guided" if guided else "verify_sample" if sample else "verify")
-        e = self.graphs.get(key)
-        return e if e is not None and e["T"] == T else self._capture_verify(key[0], key[1], T, sample, guided)
-
-    def launch_verify(self, ids, pos, slots, bt, ctx, n_rows, T: int, sample: Optional[dict] = None) -> dict:
-        """Stage + replay one verify step: ids / pos / slots host arrays of B * T rows
-        (sequence-major, padding rows slot -1), ctx / n_rows of B sequences.  Returns a handle
-        for :meth:`verified`.  ``sample``: the device sampler's arrays (keys of ``_SAMPLE_ROWS``;
-        ``u`` of B * T rows, the others of B sequences) -- the step runs the ``verify_sample`` graph;
-        with ``g_in`` (B * T rows) too, the ``verify_guided`` graph."""
-        B = len(ctx)
-        guided = sample is not None and "g_in" in sample
-        e = self._entry_verify(B, bt.shape[1], T, sample is not None, guided)
-        W = e["W"]
-        par = e["par"]
-        e["par"] ^= 1
-        if e["ev"][par] is not None:
-            e["ev"][par].synchronize()        # the copies that last used these pinned buffers are done
-        hv = {k: v.numpy() for k, v in e["h_views"][par].items()}
-        w = min(bt.shape[1], W)
-        for k, pad, val in (("slots", -1, slots), ("ids", 0, ids), ("pos", 0, pos)):
-            hv[k][:] = pad
-            hv[k][:B * T] = val
-        for k, val in (("ctx", ctx), ("n_rows", n_rows)):
-            hv[k][:] = 1
-            hv[k][:B] = val
-        hv["bt"][:] = 0
-        hv["bt"][:B, :w] = bt[:, :w]
-        if sample is not None:
-            for k, pad in self._SAMPLE_PAD.items():
-                hv[k][:] = pad
-                hv[k][:len(sample[k])] = sample[k]
-            if guided:
-                hv["g_in"][:] = -1
-                hv["g_in"][:B * T] = sample["g_in"]
-        e["dbuf"].copy_(e["h_step"][par], non_blocking=True)
-        e["g"].replay()
-        e["h_res"][par].copy_(e["res"], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        e["ev"][par] = ev
-        return {"e": e, "par": par, "B": B, "ev": ev}
-
-    def verified(self, h: dict) -> np.ndarray:
-        """tokens [B * T] int32 of a launched verify step -- the arg-max of every row, or what the
-        ``verify_sample`` / ``verify_guided`` graph drew (then ``h["n_acc"]`` holds the device's accepted counts [B]) --
-        (waits for it); sets ``h["err"]``"""
-        e = h["e"]
-        h["ev"].synchronize()
-        r = e["h_res"][h["par"]].numpy()
-        R = e["Bp"] * e["T"]
-        if e["mode"] in ("verify_sample", "verify_guided"):
-            h["n_acc"] = r[R:R + h["B"]]
-            h["err"] = int(r[R + e["Bp"]])
-        else:
-            h["err"] = int(r[R])
-        return r[:h["B"] * e["T"]]
-
-    def run(self, ids, pos, slots, bt, ctx) -> torch.Tensor:
-        """Replay one step and return its logits [B, V/tp] (device, valid until the next replay)."""
-        h = self.launch(ids, pos, slots, bt, ctx)
-        return h["e"]["out"][:h["B"]]
-
 
 class LLMEngine:
     def __init__(self, llm, kv: PagedKVCache, prefill_builder: Callable[[Any], torch.Tensor], max_batch: int = 64,
@@ -1122,10 +288,15 @@ class LLMEngine:
         # the seen-token bitmaps: the graphs' own (kept if a capture failure drops the graphs), or
         # a bare set for sampled verify steps without graphs
         self._slots: Optional[SeenSlots] = self.graphs
-        if self._slots is None and ((self.spec_sampling and self.drafter is not None) or self.spec_guided):
+        if self._slots is None and self._verify_needs_slots:
             self._slots = SeenSlots(llm, max_batch)
         self._thread = threading.Thread(target=self._loop, name=f"lumen-{name}-engine", daemon=True)
         self._thread.start()
+
+    @property
+    def _verify_needs_slots(self) -> bool:
+        """verify steps of this engine may take the sampled form, which penalises from the bitmap slots"""
+        return (self.spec_sampling and self.drafter is not None) or self.spec_guided
 
     # ------------------------------------------------------------------ public API
     @staticmethod
@@ -1229,6 +400,22 @@ class LLMEngine:
             return True
         return False
 
+    def _advance(self, reqs, toks) -> list:
+        """The step's outcome: request i takes ``toks[i]`` in order (one token of a decode step, the
+        accepted rows' tokens of a verify step), each advancing its context, up to the first that
+        finishes it.  The requests that go on are the running batch, which is returned."""
+        still = []
+        for r, ts in zip(reqs, toks):
+            for t in ts:
+                r.ctx += 1
+                if self._emit(r, int(t)):
+                    self._finish(r)
+                    break
+            else:
+                still.append(r)
+        self._running = still
+        return still
+
     @staticmethod
     def _penalised(r: GenRequest) -> bool:
         return abs(float(r.params.repetition_penalty) - 1.0) > 1e-6
@@ -1237,7 +424,7 @@ class LLMEngine:
         """``r`` enters the running batch; a penalised request takes a zeroed row of the device
         sampler's seen bitmap (none free, or no graphs: its batches sample on the host)"""
         wanted = (self.ingraph_sampling and self.graphs is not None) or \
-            (((self.spec_sampling and self.drafter is not None) or self.spec_guided) and self._slots is not None)
+            (self._verify_needs_slots and self._slots is not None)
         if wanted and self._penalised(r):
             r.seen_slot = self._slots.take_slot()
             if r.seen_slot is not None:
@@ -1420,6 +607,18 @@ class LLMEngine:
             del r.us[k]
         return r.us[n]
 
+    @staticmethod
+    def _sampler_rows(reqs) -> dict:
+        """the device sampler's per-sequence inputs (a penalised request without a bitmap slot is not
+        penalised: such a batch never gets here)"""
+        ps = [r.params for r in reqs]
+        return {"inv_t": np.array([1.0 / p.temperature if p.temperature > 0 else 1.0 for p in ps], np.float32),
+                "top_p": np.array([p.top_p for p in ps], np.float64),
+                "penalty": np.array([float(p.repetition_penalty) if r.seen_slot is not None else 1.0
+                                     for p, r in zip(ps, reqs)], np.float32),
+                "greedy": np.array([p.temperature <= 0 for p in ps], np.int32),
+                "seen_slot": np.array([-1 if r.seen_slot is None else r.seen_slot for r in reqs], np.int32)}
+
     def _sample_inputs(self, reqs, ahead: int, fed: bool, guided: bool = False) -> dict:
         """per-row inputs of the device sampler for the step that yields token len(tokens) + ahead;
         ``fed``: the step gets its input tokens from the host (not a look-ahead); ``guided``: the
@@ -1434,14 +633,8 @@ class LLMEngine:
                 r.seen_n = n                      # this step marks tokens[-1]
             else:
                 r.seen_n = n + 1                  # ... and this one the token the step before it draws
-        ps = [r.params for r in reqs]
-        out = {"inv_t": np.array([1.0 / p.temperature if p.temperature > 0 else 1.0 for p in ps], np.float32),
-               "top_p": np.array([p.top_p for p in ps], np.float64),
-               "penalty": np.array([float(p.repetition_penalty) if r.seen_slot is not None else 1.0
-                                    for p, r in zip(ps, reqs)], np.float32),
-               "greedy": np.array([p.temperature <= 0 for p in ps], np.int32),
-               "seen_slot": np.array([-1 if r.seen_slot is None else r.seen_slot for r in reqs], np.int32),
-               "u": np.array([self._uniform(r, len(r.tokens) + ahead) for r in reqs], np.float64)}
+        out = self._sampler_rows(reqs)
+        out["u"] = np.array([self._uniform(r, len(r.tokens) + ahead) for r in reqs], np.float64)
         if guided:
             # a fed step carries the state the host derived from the request's tokens; a look-ahead
             # step reads the one the step before it stored, so a discarded look-ahead step that is
@@ -1450,6 +643,14 @@ class LLMEngine:
             out["g_slot"] = np.array([r.guide_slot if g else -1 for r, g in zip(reqs, gd)], np.int32)
             out["g_in"] = np.array([r.guide_base + r.gstate if g and fed else -1 for r, g in zip(reqs, gd)], np.int32)
         return out
+
+    def _graphs_failed(self, e: BaseException) -> None:
+        """a capture or replay failed: eager launches from now on.  Not under TP, where the ranks
+        must not diverge: the error is raised instead of falling back"""
+        if self.sync is not None:
+            raise e
+        log.warning("hipGraph decode disabled: %s", e)
+        self.graphs = None
 
     def _graph_ready(self, reqs, mode: str = "greedy") -> bool:
         """the step's graph exists or captures now (a capture failure disables graphs).  Under
@@ -1461,11 +662,10 @@ class LLMEngine:
         if self.sync is not None:
             return True
         try:
-            self.graphs._entry(len(reqs), w, mode)
+            self.graphs.ensure(len(reqs), w, mode)
             return True
-        except Exception as e:  # noqa: BLE001 - capture unsupported: eager launches from now on
-            log.warning("hipGraph decode disabled: %s", e)
-            self.graphs = None
+        except Exception as e:  # noqa: BLE001 - capture unsupported
+            self._graphs_failed(e)
             return False
 
     def _step_inputs(self, reqs, ahead: int):
@@ -1571,15 +771,10 @@ class LLMEngine:
             if r.seen_slot is not None and r.seen_n not in (n - 1, n):
                 self._slots.write_slot(r.seen_slot, r.tokens[:-1])
                 r.seen_n = n - 1
-        ps = [r.params for r in reqs]
-        return {"inv_t": np.array([1.0 / p.temperature if p.temperature > 0 else 1.0 for p in ps], np.float32),
-                "top_p": np.array([p.top_p for p in ps], np.float64),
-                "penalty": np.array([float(p.repetition_penalty) if r.seen_slot is not None else 1.0
-                                     for p, r in zip(ps, reqs)], np.float32),
-                "greedy": np.array([p.temperature <= 0 for p in ps], np.int32),
-                "seen_slot": np.array([-1 if r.seen_slot is None else r.seen_slot for r in reqs], np.int32),
-                "u": np.array([self._uniform(r, len(r.tokens) + i, len(r.tokens)) for r in reqs for i in range(T)],
-                              np.float64)}
+        out = self._sampler_rows(reqs)
+        out["u"] = np.array([self._uniform(r, len(r.tokens) + i, len(r.tokens)) for r in reqs for i in range(T)],
+                            np.float64)
+        return out
 
     @torch.no_grad()
     def _verify(self, reqs, drafts) -> None:
@@ -1633,9 +828,8 @@ class LLMEngine:
                 h = self.graphs.launch_verify(ids, pos, slots, bt, ctx, n_rows, T, sample)
                 am = self.graphs.verified(h)
                 n_acc = h.get("n_acc")
-            except Exception as e:  # noqa: BLE001 - capture unsupported: eager launches from now on
-                log.warning("hipGraph decode disabled: %s", e)
-                self.graphs = None
+            except Exception as e:  # noqa: BLE001 - capture unsupported
+                self._graphs_failed(e)
                 if smp:       # the failed launch may have left the bitmap rows anywhere
                     for r in reqs:
                         r.seen_n = -1
@@ -1669,9 +863,7 @@ class LLMEngine:
             acc.append(j)
         if n_acc is not None and acc != [int(x) for x in n_acc[:B]]:      # before anything is emitted
             raise RuntimeError(f"verify step: the device accepted {list(n_acc[:B])} draft tokens, the host {acc}")
-        still = []
-        for b, (r, d) in enumerate(zip(reqs, drafts)):
-            row, j = am[b * T:b * T + 1 + len(d)], acc[b]
+        for r, d, j in zip(reqs, drafts, acc):
             if smp:
                 r.seen_n = len(r.tokens) + j      # the accept kernel marked tokens[-1] and the accepted draft tokens
             self.stats["spec_drafted"] += len(d)
@@ -1679,17 +871,7 @@ class LLMEngine:
             if r.draft_forced:
                 self.stats["spec_forced_drafted"] += len(d)
                 self.stats["spec_forced_accepted"] += j
-            done = False
-            for t in row[:j + 1]:
-                r.ctx += 1
-                if self._emit(r, int(t)):
-                    done = True
-                    break
-            if done:
-                self._finish(r)
-            else:
-                still.append(r)
-        self._running = still
+        self._advance(reqs, [am[b * T:b * T + j + 1] for b, j in enumerate(acc)])
 
     @torch.no_grad()
     def _decode(self) -> None:
@@ -1742,14 +924,7 @@ class LLMEngine:
                 self._pending = None
                 raise TPGroupUnavailable("tensor-parallel peer not responding (IPC all-reduce timed out)")
             self.stats["decode_steps"] += 1
-            still = []
-            for r, t in zip(reqs, toks):
-                r.ctx += 1
-                if self._emit(r, t):
-                    self._finish(r)
-                else:
-                    still.append(r)
-            self._running = still
+            still = self._advance(reqs, [(t,) for t in toks])
             if late and len(still) == B and self._can_look_ahead(reqs) and self._spec_drafts(reqs) is None:
                 nxt = self._launch_greedy(np.array([r.tokens[-1] for r in reqs], np.int64),
                                           self._step_inputs(reqs, 0), spec,      # ctx already advanced
@@ -1760,10 +935,7 @@ class LLMEngine:
             return
         self._pending = None
         ids = np.array([r.tokens[-1] for r in reqs], np.int64)
-        pos = np.array([r.ctx for r in reqs], np.int32)
-        slots = np.concatenate([self.kv.slots(r.rid, r.ctx, 1) for r in reqs])
-        bt = self.kv.block_table([r.rid for r in reqs])
-        ctx = pos + 1
+        pos, slots, bt, ctx = self._step_inputs(reqs, 0)
         graph = self.graphs is not None and bt.shape[1] <= self.graphs.max_blocks
         if self.sync is not None:
             self.sync.send_decode(ids, pos, slots, bt, ctx, spec, graph)
@@ -1773,14 +945,7 @@ class LLMEngine:
         comm = getattr(self.llm, "comm", None)
         if comm is not None:
             comm.check()    # before emitting; the tokens' D2H already waited for the step
-        still = []
-        for r, t in zip(reqs, toks):
-            r.ctx += 1
-            if self._emit(r, t):
-                self._finish(r)
-            else:
-                still.append(r)
-        self._running = still
+        self._advance(reqs, [(t,) for t in toks])
 
     def _launch_greedy(self, ids, inputs, spec, sample: Optional[dict] = None) -> dict:
         """One in-graph-sampled step (``ids`` None: look-ahead, ids from the device); under TP the
@@ -1790,11 +955,8 @@ class LLMEngine:
             self.sync.send_decode(ids, *inputs, spec, graph=True, ingraph=True)
         try:
             return self.graphs.launch(ids, *inputs, sample=sample)
-        except Exception:
-            if self.sync is not None:
-                raise            # TP ranks must not diverge
-            log.warning("hipGraph decode disabled", exc_info=True)
-            self.graphs = None
+        except Exception as e:
+            self._graphs_failed(e)
             raise
 
     def _decode_step(self, ids, pos, slots, bt, ctx, graph: bool = True) -> torch.Tensor:
@@ -1803,10 +965,7 @@ class LLMEngine:
             try:
                 return self.graphs.run(ids, pos, slots, bt, ctx)
             except Exception as e:  # noqa: BLE001 - capture unsupported: fall back to eager launches
-                if self.sync is not None:
-                    raise            # TP ranks must not diverge: surface instead of falling back
-                log.warning("hipGraph decode disabled: %s", e)
-                self.graphs = None
+                self._graphs_failed(e)
         return self.llm.decode(h2d(ids, d), h2d(pos, d), h2d(slots, d), self.kv, h2d(bt, d), h2d(ctx, d),
                                workspace=self._ws)
 
