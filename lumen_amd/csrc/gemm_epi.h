@@ -200,6 +200,19 @@ __device__ __forceinline__ void add8(float* v, const uint16_t* p) {
   for (int q = 0; q < 8; ++q) v[q] += f[q];
 }
 
+// Activation of an epilogue piece.  ACT >= 0: that activation, compiled in (no branch); ACT_RT: the
+// run-time switch over GemmEpi::act.  Same act_fn per element either way.
+constexpr int ACT_RT = -1;
+template <int ACT, int N>
+__device__ __forceinline__ void epi_act(float* v, int act) {
+  if constexpr (ACT == ACT_RT) {
+    if (act) apply_act_n<N>(v, act);
+  } else if constexpr (ACT != ACT_NONE) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) v[q] = act_fn<ACT>(v[q]);
+  }
+}
+
 // Apply the epilogue to 16 consecutive columns [n, n+16) of row m and store.  AFF: the output
 // affine (GemmEpi::aff_s) is live (bf16 output, full 16-column pieces: the conv host code checks).
 template <bool WT, bool AFF = false>
@@ -324,7 +337,7 @@ __device__ __forceinline__ void epi_store16_t(float* v, int m, int n, int M, int
 
 // 8-column form (no SwiGLU): [n, n+8) of row m.  Used by the row-coalesced
 // 256x256 epilogue, where 16 consecutive lanes store 256 contiguous bytes.
-template <bool WT>
+template <bool WT, int ACT = ACT_RT>
 __device__ __forceinline__ void epi_store8_t(float* v, int m, int n, int M, int N, void* __restrict__ C, int64_t ldc,
                                              const GemmEpi& ep, __amdgpu_buffer_rsrc_t rs) {
   if (m >= M || n >= N) return;
@@ -351,7 +364,7 @@ __device__ __forceinline__ void epi_store8_t(float* v, int m, int n, int M, int 
       }
     }
   }
-  if (ep.act) apply_act_n<8>(v, ep.act);
+  epi_act<ACT, 8>(v, ep.act);
   if (ep.prelu) {
     float sl[8];
     if (full) unpack8(*(const u32x4_t*)(ep.prelu + n), sl);
@@ -437,13 +450,13 @@ __device__ __forceinline__ void epi_store16_fast(float* v, int64_t m, int n, voi
 
 // LN-folded fast path (FK = 5 of the ping-pong kernels): v[q] = v[q] * rs + ro * cs[q] + cb[q], then the
 // activation, bf16 store of n_cols (8 or 16) columns.  cs / cb: the lane's columns of col_aff, prefetched.
-template <bool WT, int NC>
+template <bool WT, int NC, int ACT = ACT_RT>
 __device__ __forceinline__ void epi_store_lnf(float* v, int64_t m, int n, void* __restrict__ C, int64_t ldc,
                                               const GemmEpi& ep, float rs, float ro, const float* cs, const float* cb,
                                               __amdgpu_buffer_rsrc_t r) {
 #pragma unroll
   for (int q = 0; q < NC; ++q) v[q] = v[q] * rs + (ro * cs[q] + cb[q]);
-  if (ep.act) apply_act_n<NC>(v, ep.act);
+  epi_act<ACT, NC>(v, ep.act);
 #pragma unroll
   for (int h = 0; h < NC / 8; ++h) st16<WT>(C, r, (m * ldc + n + 8 * h) * 2, pack8(v + 8 * h));
 }

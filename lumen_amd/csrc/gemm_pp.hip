@@ -40,7 +40,9 @@ __device__ __forceinline__ void pp_barrier() {
 // Direct-store epilogue (DS kernels): the lane holds row m0 + qm*128 + wm*64 + i*16 + (lane & 15),
 // columns n0 + qn*128 + wn*32 + 8*(lane >> 4) + [0, 8) in acc[qm][qn][i][0..1][0..3]; 16 passes of one
 // 16-byte store each.  Bias / residual / LN-fold operands are loaded up front (residual RD passes ahead).
-template <bool WT, int FK>
+// ACT: the activation, compiled in (epi_act): with the run-time switch every pass was its own island of
+// branches around nine activation bodies, and no load, store or VALU could move across a pass boundary.
+template <bool WT, int FK, int ACT>
 __device__ __forceinline__ void pp_epilogue_direct(const f32x4_t (&acc)[2][2][4][2], int m0, int n0, int M, int N,
                                                    void* __restrict__ C, int64_t ldc, const GemmEpi& ep, int wm,
                                                    int wn, int lane, const float* aff_lds = nullptr) {
@@ -115,13 +117,13 @@ __device__ __forceinline__ void pp_epilogue_direct(const f32x4_t (&acc)[2][2][4]
     }
     const int m = row_of(p), n = col_of(qn);
     if constexpr (FL) {
-      epi_store_lnf<WT, 8>(v, m, n, C, ldc, ep, lrs[p >> 1], lro[p >> 1], lcs + qn * 8, lcb + qn * 8, crs);
+      epi_store_lnf<WT, 8, ACT>(v, m, n, C, ldc, ep, lrs[p >> 1], lro[p >> 1], lcs + qn * 8, lcb + qn * 8, crs);
     } else if constexpr (fast) {
       float f[8];
       unpack8(bq[qn], f);
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = v[q] * ep.alpha + f[q];
-      if (ep.act) apply_act_n<8>(v, ep.act);
+      epi_act<ACT, 8>(v, ep.act);
       if constexpr (FR) {
         unpack8(rz[p % RD], f);
 #pragma unroll
@@ -130,7 +132,7 @@ __device__ __forceinline__ void pp_epilogue_direct(const f32x4_t (&acc)[2][2][4]
       }
       st16<WT>(C, crs, ((int64_t)m * ldc + n) * 2, pack8(v));
     } else {
-      epi_store8_t<WT>(v, m, n, M, N, C, ldc, ep, crs);
+      epi_store8_t<WT, ACT>(v, m, n, M, N, C, ldc, ep, crs);
     }
   });
 }
@@ -146,8 +148,9 @@ __device__ __forceinline__ void vm_wait_n() {
 // NPH: phases per K-tile (4 or 2).  PRIO 0: s_setprio(1) around every MFMA cluster;
 // PRIO 1: static priority 1 for the lagging group (MI355X_MICROARCH "Two waves per SIMD" 4).
 // DS: direct-store epilogue (gemm_epi.h swzb): transposed accumulators, 16-byte stores straight
-// from registers, no LDS staging (no SwiGLU).
-template <bool WT, int FK, int PRIO, int NPH, bool DS = false>
+// from registers, no LDS staging (no SwiGLU), the activation ACT compiled in; the LDS-staged form
+// switches on GemmEpi::act at run time (ACT_RT).
+template <bool WT, int FK, int PRIO, int NPH, bool DS = false, int ACT = ACT_RT>
 __global__ void __launch_bounds__(512)
 gemm_pp_kernel(const uint16_t* __restrict__ A, int64_t lda, const uint16_t* __restrict__ W, int64_t ldw,
                void* __restrict__ C, int64_t ldc, int M, int N, int K, GemmEpi ep, int group_m) {
@@ -370,7 +373,7 @@ gemm_pp_kernel(const uint16_t* __restrict__ A, int64_t lda, const uint16_t* __re
   const int64_t t_loop = ep.dbg ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
 
   if constexpr (DS) {
-    pp_epilogue_direct<WT, FK>(acc, m0, n0, M, N, C, ldc, ep, wm, wn, lane, PRE ? aff_lds : nullptr);
+    pp_epilogue_direct<WT, FK, ACT>(acc, m0, n0, M, N, C, ldc, ep, wm, wn, lane, PRE ? aff_lds : nullptr);
   } else {
   // ---- epilogue: per-wave 16-row slabs through LDS (bias / residual prefetched on the FAST path)
   constexpr int LDSTR = 68;
@@ -457,19 +460,26 @@ gemm_pp_kernel(const uint16_t* __restrict__ A, int64_t lda, const uint16_t* __re
   }
 }
 
-template <bool WT, int FK, int PRIO, int NPH, bool DS = false>
+template <bool WT, int FK, int PRIO, int NPH, bool DS = false, int ACT = ACT_RT>
 static void launch_pp_t(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, void* C, int64_t ldc, int M,
                         int N, int K, const GemmEpi& ep, int group_m, hipStream_t stream, int splits = 1) {
   const dim3 tiles(((M + 255) / 256) * ((N + 255) / 256), splits);
   const size_t lds = 2 * G_BUF + (DS && FK == 5 ? 4096 : 0);   // + the LN-fold affine stage
   static bool attr_set = false;
   if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm_pp_kernel<WT, FK, PRIO, NPH, DS>,
+    hipFuncSetAttribute((const void*)gemm_pp_kernel<WT, FK, PRIO, NPH, DS, ACT>,
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
-  hipLaunchKernelGGL((gemm_pp_kernel<WT, FK, PRIO, NPH, DS>), dim3(tiles), dim3(512), lds, stream, A, lda, W, ldw,
+  hipLaunchKernelGGL((gemm_pp_kernel<WT, FK, PRIO, NPH, DS, ACT>), dim3(tiles), dim3(512), lds, stream, A, lda, W, ldw,
                      C, ldc, M, N, K, ep, group_m);
+}
+
+// The (FK, activation) pairs the direct-store kernels are compiled for: none / quick_gelu / gelu (the CLIP
+// towers' and BERT's); the bias + residual epilogues (out-proj, fc2) without an activation only.  gemm_pp()
+// runs every other pair on the LDS-staged form of the same tile code.
+static constexpr bool ds_compiled(int fk, int act) {
+  return act == ACT_NONE || (fk != 3 && fk != 4 && (act == ACT_QUICK_GELU || act == ACT_GELU));
 }
 
 template <int FK>
@@ -481,7 +491,15 @@ static void launch_pp_fk(const uint16_t* A, int64_t lda, const uint16_t* W, int6
   if (ds) {   // direct-store epilogue: the production two-phase, static-priority form only
     // (r5 A/Bs, profiles/r5_gemm_pp_ds_v1.txt: write-through C stores and 8 / 16 residual rows in flight
     // both lost to plain stores with 4 rows in flight; those variants were removed in r6)
-    launch_pp_t<false, FK, 1, 2, true>(A, lda, W, ldw, C, ldc, M, N, K, ep, group_m, stream);
+    // (the run-time activation switch in this epilogue lost to the compiled activation, 6,611 vs 6,719 img/s,
+    // profiles/gemm_epilogue_act_v1.txt, and was removed)
+#define LM_PP_DS_ACT(ACTV)                                                                                      \
+    if constexpr (ds_compiled(FK, ACTV))                                                                        \
+      if (ep.act == ACTV) launch_pp_t<false, FK, 1, 2, true, ACTV>(A, lda, W, ldw, C, ldc, M, N, K, ep, group_m, stream);
+    LM_PP_DS_ACT(ACT_NONE)
+    LM_PP_DS_ACT(ACT_QUICK_GELU)
+    LM_PP_DS_ACT(ACT_GELU)
+#undef LM_PP_DS_ACT
     return;
   }
   if (two) {
@@ -518,7 +536,7 @@ constexpr int PPS_STR = 36;                       // epilogue staging row stride
 constexpr int PPS_WAVE = 16 * PPS_STR * 4;        // bytes per wave
 constexpr int PPS_LDS = 2 * G_BUF + 8 * PPS_WAVE;
 
-template <int FK, int PRIO, bool DS = false>
+template <int FK, int PRIO, bool DS = false, int ACT = ACT_RT>
 __global__ void __launch_bounds__(512)
 gemm_pps_kernel(const uint16_t* __restrict__ A, int64_t lda, const uint16_t* __restrict__ W, int64_t ldw,
                 void* __restrict__ C, int64_t ldc, int M, int N, int K, GemmEpi ep, int group_m) {
@@ -692,7 +710,7 @@ gemm_pps_kernel(const uint16_t* __restrict__ A, int64_t lda, const uint16_t* __r
     const int64_t t_loop = ep.dbg ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
 
     if constexpr (DS) {
-      pp_epilogue_direct<false, FK>(acc, m0, n0, M, N, C, ldc, ep, wm, wn, lane);
+      pp_epilogue_direct<false, FK, ACT>(acc, m0, n0, M, N, C, ldc, ep, wm, wn, lane);
       after = 1;
     } else {
       // ---- C epilogue: 16 passes (qm, i, qn) of 16 rows x 32 columns through this wave's
@@ -793,7 +811,7 @@ static int pp_num_cus() {
   return n;
 }
 
-template <int FK, int PRIO, bool DS = false>
+template <int FK, int PRIO, bool DS = false, int ACT = ACT_RT>
 static void launch_pps_t(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, void* C, int64_t ldc, int M,
                          int N, int K, const GemmEpi& ep, int group_m, hipStream_t stream) {
   const int tiles = (M / 256) * (N / 256);
@@ -803,16 +821,30 @@ static void launch_pps_t(const uint16_t* A, int64_t lda, const uint16_t* W, int6
   const int lds = DS ? 2 * G_BUF : PPS_LDS;
   static bool attr_set = false;
   if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm_pps_kernel<FK, PRIO, DS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute((const void*)gemm_pps_kernel<FK, PRIO, DS, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                        lds);
     attr_set = true;
   }
-  hipLaunchKernelGGL((gemm_pps_kernel<FK, PRIO, DS>), dim3(grid), dim3(512), lds, stream, A, lda, W, ldw, C, ldc, M,
+  hipLaunchKernelGGL((gemm_pps_kernel<FK, PRIO, DS, ACT>), dim3(grid), dim3(512), lds, stream, A, lda, W, ldw, C, ldc, M,
                      N, K, ep, group_m);
+}
+
+template <int FK>
+static void launch_pps_ds(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, void* C, int64_t ldc, int M,
+                          int N, int K, const GemmEpi& ep, int group_m, hipStream_t stream) {
+#define LM_PPS_DS_ACT(ACTV)                                                                                     \
+  if constexpr (ds_compiled(FK, ACTV))                                                                          \
+    if (ep.act == ACTV) launch_pps_t<FK, 1, true, ACTV>(A, lda, W, ldw, C, ldc, M, N, K, ep, group_m, stream);
+  LM_PPS_DS_ACT(ACT_NONE)
+  LM_PPS_DS_ACT(ACT_QUICK_GELU)
+  LM_PPS_DS_ACT(ACT_GELU)
+#undef LM_PPS_DS_ACT
 }
 
 hipError_t gemm_pp(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, void* C, int64_t ldc, int M,
                    int N, int K, const GemmEpi& ep, int group_m, int variant, hipStream_t stream) {
-  // variants 8 / 9: 6 / 7 with the direct-store epilogue (pp_epilogue_direct; not for SwiGLU)
+  // variants 8 / 9: 6 / 7 with the direct-store epilogue (pp_epilogue_direct; not for SwiGLU, and for the
+  // compiled (FK, activation) pairs only: ds_compiled)
   bool ds = false;
   if (variant >= 8) {
     variant -= 2;
@@ -831,7 +863,8 @@ hipError_t gemm_pp(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ld
       const bool prio1 = (variant & 2) != 0;
 #define LM_PPS_CASE(FKV)                                                                                     \
       case FKV:                                                                                                 \
-        if (ds) launch_pps_t<FKV, 1, true>(A, lda, W, ldw, C, ldc, M, N, K, ep, group_m, stream);               \
+        if (ds && ds_compiled(FKV, ep.act))                                                                     \
+          launch_pps_ds<FKV>(A, lda, W, ldw, C, ldc, M, N, K, ep, group_m, stream);                             \
         else if (prio1) launch_pps_t<FKV, 1>(A, lda, W, ldw, C, ldc, M, N, K, ep, group_m, stream);             \
         else launch_pps_t<FKV, 0>(A, lda, W, ldw, C, ldc, M, N, K, ep, group_m, stream);                        \
         break;
@@ -856,6 +889,7 @@ hipError_t gemm_pp(const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ld
   const bool lnf = ep.row_aff && !ep.bias && !ep.residual && ep.alpha == 1.f && fast;
   const int fk = lnf ? 5 : fast && !ep.row_aff ? 1 + (ep.bias ? 1 : 0) + (ep.residual ? 2 : 0) : 0;
   const bool prio1 = (variant & 2) != 0, two = (variant & 4) != 0;
+  ds = ds && ds_compiled(fk, ep.act);
   switch (fk) {
     case 1: launch_pp_fk<1>(A, lda, W, ldw, C, ldc, M, N, K, ep, group_m, wt, prio1, two, ds, stream); break;
     case 2: launch_pp_fk<2>(A, lda, W, ldw, C, ldc, M, N, K, ep, group_m, wt, prio1, two, ds, stream); break;
