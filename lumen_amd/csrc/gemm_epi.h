@@ -77,15 +77,6 @@ struct MxArgs {
   int skip_c;        // SwiGLU with q8: no bf16 output
 };
 
-// Launch plan of an fp8-weight decode GEMM (gemm_w8.hip): column tiles per wave, K splits and
-// the K chunk per split.  The host sizes the split-K slabs / counters from the same plan.
-struct W8DecPlan {
-  int tpw;
-  int ks;
-  int kchunk;
-};
-W8DecPlan w8_dec_plan(int M, int N, int K);
-
 // rstd of the M (<= 32) A rows of a norm-folded decode GEMM into LDS (wave w: rows w, w + NWV, ...);
 // the caller's next __syncthreads publishes it.  K = row length (the normalised width).
 template <int NWV>
@@ -487,57 +478,6 @@ __device__ __forceinline__ void epi_store16_dec(float* v, float rs, int m, int n
     }
     ep.ssq_out[(int64_t)m * ep.ssq_tiles + (n >> 4)] = s;
   }
-}
-
-// In-launch split-K reduction of the skinny decode GEMMs (the counter form of the
-// write-through hand-off, cdna_hip_programming.md §6 G16 / MI355X_MICROARCH.md: per-XCD
-// L2s are not coherent, and a __threadfence() per block costs ~4x the whole GEMM).
-// Called by every thread once `red` ([4 waves][rows][17] LDS partials) is complete:
-//   1. the workgroup's summed partial tile goes to its fp32 slab with agent-scope
-//      (sc1, write-through) stores, drained by every wave before the barrier;
-//   2. lane 0 draws a ticket from the tile's counter (relaxed agent fetch_add); the
-//      workgroup that draws nsplit-1 arrived last, resets the counter (buffer is
-//      all-zero between kernels) and tells its waves through red's padding column;
-//   3. the last arriver reads every slab with sc1 loads and sums them in split order
-//      (deterministic, independent of arrival order) into red[1][m][c].
-// No release/acquire fences: sc1 stores leave L2 before the ticket, sc1 loads bypass L1.
-template <int NWV, int ROWS>
-__device__ __forceinline__ bool splitk_reduce_last(float (&red)[NWV][ROWS][17], float* ws, uint32_t* cnt, int M, int N,
-                                                   int n0) {
-  const int tid = threadIdx.x;
-  const int64_t slab = (int64_t)M * N;
-  float* mine = ws + (int64_t)blockIdx.y * slab;
-  for (int idx = tid; idx < ROWS * 16; idx += blockDim.x) {
-    const int m = idx >> 4, c = idx & 15;
-    if (m < M && n0 + c < N) {
-      float v = 0.f;
-#pragma unroll
-      for (int w = 0; w < NWV; ++w) v += red[w][m][c];
-      __hip_atomic_store(mine + (int64_t)m * N + n0 + c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const uint32_t prev = __hip_atomic_fetch_add(cnt + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = prev == gridDim.y - 1;
-    if (last) __hip_atomic_store(cnt + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    red[0][0][16] = last ? 1.f : 0.f;
-  }
-  __syncthreads();
-  if (red[0][0][16] == 0.f) return false;
-  for (int idx = tid; idx < ROWS * 16; idx += blockDim.x) {
-    const int m = idx >> 4, c = idx & 15;
-    float v = 0.f;
-    if (m < M && n0 + c < N) {
-      const float* p = ws + (int64_t)m * N + n0 + c;
-      for (int s = 0; s < (int)gridDim.y; ++s)
-        v += __hip_atomic_load(p + s * slab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    red[1][m][c] = v;
-  }
-  __syncthreads();
-  return true;
 }
 
 }  // namespace lumen

@@ -1,12 +1,9 @@
-// Weight-only 4-bit group-quantised GEMMs for the LLM decoder (gemm_w4.hip).
+// Weight-only 4-bit group-quantised GEMMs for the LLM decoder (gemm_w4.hip).  The decode launch
+// plan (w4_dec_plan) is declared with the scaffold, gemm_wdec.h.
 #pragma once
-#include "gemm_epi.h"
+#include "gemm_wdec.h"
 
 namespace lumen {
-
-// Launch plan of a 4-bit-weight decode GEMM, 4 < M <= 32 (tpw unused: one 16-column tile per
-// workgroup).  The host sizes the split-K slabs / counters from the same plan.
-W8DecPlan w4_dec_plan(int M, int N, int K);
 
 // C[M, N] = epi(A[M, K] . dq(W4)[N, K]^T), dq(W4)[n, k] = code[n, k] * scale[n, k / G] + wmin[n, k / G].
 // W4: uint8 [N, K / 2], two codes per byte, low nibble = even k.  params: fp16 [N, K / G, 2]

@@ -9,10 +9,12 @@
 // one 4-byte load per group, G in {32, 128}.  Decode GEMMs are HBM-bound on the weight bytes:
 // 4 bits + 32 / G bits of parameters per weight instead of fp8's 8.
 //
-//  * gemv_w4_rows_kernel (M <= 4): the row-streaming GEMV of gemm_w8.hip.  A lane's 16-byte
-//    load carries 32 k values = (a quarter of) one group; its (scale, wmin) dword is loaded
-//    with it.  The codes never become weights: a dword's nibbles i and i + 4 are masked into
-//    one bf16 pair (0x4300 | c = 128 + c exactly), the activations are paired the same way,
+// What is specific to 4-bit groups lives here; the pipeline driver, row-GEMV prologue / tail and
+// split-K hand-off are the decode scaffold (gemm_wdec.h), the prefill tile is gemm_wtile.h.
+//  * gemv_w4_rows_kernel (M <= 4): 2048-wide k steps.  A lane's 16-byte load carries 32 k
+//    values = (a quarter of) one group; its (scale, wmin) dword is loaded with it.  The codes
+//    never become weights: a dword's nibbles i and i + 4 are masked into one bf16 pair
+//    (0x4300 | c = 128 + c exactly), the activations are paired the same way,
 //    and with d = sum a_k (128 + c_k), sa = sum a_k over the lane's 32 k
 //        sum a_k (c_k scale + wmin) = scale * d + (wmin - 128 scale) * sa      (fp32).
 //  * gemm_skinny_w4_kernel (4 < M <= 32): split-K MFMA kernel; lane group g owns k in
@@ -20,16 +22,14 @@
 //    feeds four 16x16x32 MFMAs.  G = 128: the exact codes go into the MFMA and the group
 //    parameters scale the block's partial sums; G = 32: codes are widened in registers,
 //    bf16(code * scale + wmin), one fp32 fma per weight.
-//  * gemm_w4_kernel (M > 32, prefill): the register-staged 2-stage tile of gemm_w8_kernel; a
-//    chunk of 8 codes (one dword) is widened to 8 bf16 on its way into the swizzled LDS image.
-#include <cstdlib>
-
+//  * W4Tile (M > 32, prefill): policy of gemm_wtile_kernel; a chunk of 8 codes (one dword) and
+//    its group's parameter dword; K % 64 == 32 (G = 32 shards) runs as a zero-filled K tail.
 #include "common.h"
 #include "gemm_w4.h"
+#include "gemm_wdec.h"
+#include "gemm_wtile.h"
 
 namespace lumen {
-
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float h2f_lo(uint32_t p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p & 0xffffu)); }
 __device__ __forceinline__ float h2f_hi(uint32_t p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p >> 16)); }
@@ -44,18 +44,6 @@ __device__ __forceinline__ u32x4_t w4x8_to_bf16(const uint32_t w, const float s,
     o[b] = pack2bf(fmaf(e, s, mn), fmaf(d, s, mn));
   }
   return o;
-}
-
-// t + <8 bf16 of x, 8 bf16 of y> on v_dot2c_f32_bf16 (pairs taken by shuffling a bf16x8 view,
-// see gemm_w8.hip)
-__device__ __forceinline__ float dot8_bf16_w4(const u32x4_t x, const u32x4_t y, float t) {
-  const bf16x8_t xv = __builtin_bit_cast(bf16x8_t, x), yv = __builtin_bit_cast(bf16x8_t, y);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const bf16x2_t p = {xv[2 * j], xv[2 * j + 1]}, q = {yv[2 * j], yv[2 * j + 1]};
-    t = __builtin_amdgcn_fdot2_f32_bf16(p, q, t, false);
-  }
-  return t;
 }
 
 // ============================================================================ decode, M <= 4
@@ -77,33 +65,8 @@ __global__ void __launch_bounds__(256) gemv_w4_rows_kernel(const uint16_t* __res
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n0 = blockIdx.x * 16;
 
-  // ---- epilogue operands first
-  constexpr int SSQ4 = 4;   // float4 ssq loads per lane and row: K <= 4 * 4 * 64 * 16 = 16384
-  const bool rs_pre = MR <= 2 && ep.norm && ep.ssq_in != nullptr && K <= SSQ4 * 4 * 64 * 16;
-  f32x4_t ssq_v[MR <= 2 ? MR : 1][SSQ4];
-  if (rs_pre) {   // wave-uniform
-    const int n4 = ep.ssq_tiles >> 2;
-#pragma unroll
-    for (int m = 0; m < (MR <= 2 ? MR : 1); ++m) {
-      const f32x4_t* p = (const f32x4_t*)(ep.ssq_in + (int64_t)min(m, M - 1) * ep.ssq_tiles);
-#pragma unroll
-      for (int j = 0; j < SSQ4; ++j) ssq_v[m][j] = p[min(lane + j * 64, n4 - 1)];
-    }
-  }
-  const int prow = min(lane, M - 1);
-  const bool full16 = n0 + 16 <= N;
-  const bool pre_bias = ep.bias && !ep.bias_f32 && full16;
-  const bool pre_res = ep.residual && full16;
-  u32x4_t pre_b[2] = {(u32x4_t){0u, 0u, 0u, 0u}, (u32x4_t){0u, 0u, 0u, 0u}};
-  u32x4_t pre_r[2] = {(u32x4_t){0u, 0u, 0u, 0u}, (u32x4_t){0u, 0u, 0u, 0u}};
-  if (pre_bias) {
-    pre_b[0] = *(const u32x4_t*)((const uint16_t*)ep.bias + n0);
-    pre_b[1] = *(const u32x4_t*)((const uint16_t*)ep.bias + n0 + 8);
-  }
-  if (pre_res) {
-    pre_r[0] = *(const u32x4_t*)(ep.residual + (int64_t)prow * ep.ldr + n0);
-    pre_r[1] = *(const u32x4_t*)(ep.residual + (int64_t)prow * ep.ldr + n0 + 8);
-  }
+  RowPre<MR> pre;   // epilogue operands first
+  pre.load(ep, M, N, K, n0, lane);
 
   // ---- weight stream
   const int r0 = n0 + wid * R;
@@ -159,7 +122,7 @@ __global__ void __launch_bounds__(256) gemv_w4_rows_kernel(const uint16_t* __res
             const u32x4_t a = ab[slot][u][m][j];
             q[m][j] = (u32x4_t){(a[0] & 0xffffu) | (a[2] << 16), (a[0] >> 16) | (a[2] & 0xffff0000u),
                                 (a[1] & 0xffffu) | (a[3] << 16), (a[1] >> 16) | (a[3] & 0xffff0000u)};
-            sa[m] = dot8_bf16_w4(a, ones, sa[m]);
+            sa[m] = dot8_bf16(a, ones, sa[m]);
           }
         }
 #pragma unroll
@@ -174,7 +137,7 @@ __global__ void __launch_bounds__(256) gemv_w4_rows_kernel(const uint16_t* __res
             const u32x4_t e = {(w & 0x000f000fu) | 0x43004300u, ((w >> 4) & 0x000f000fu) | 0x43004300u,
                                ((w >> 8) & 0x000f000fu) | 0x43004300u, ((w >> 12) & 0x000f000fu) | 0x43004300u};
 #pragma unroll
-            for (int m = 0; m < MR; ++m) d[m] = dot8_bf16_w4(e, q[m][j], d[m]);
+            for (int m = 0; m < MR; ++m) d[m] = dot8_bf16(e, q[m][j], d[m]);
           }
 #pragma unroll
           for (int m = 0; m < MR; ++m) acc[r][m] += fmaf(s, d[m], off * sa[m]);
@@ -184,30 +147,7 @@ __global__ void __launch_bounds__(256) gemv_w4_rows_kernel(const uint16_t* __res
   };
   const int nfull = K >> 11;
   const int nch = nfull / U;
-  if (nch > 0) {
-    issue(0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    int c = 0;
-    for (; c + 2 < nch; c += 2) {
-      issue(1, (c + 1) * U);
-      __builtin_amdgcn_sched_barrier(0);
-      consume(0, U);
-      __builtin_amdgcn_sched_barrier(0);
-      issue(0, (c + 2) * U);
-      __builtin_amdgcn_sched_barrier(0);
-      consume(1, U);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (c + 1 < nch) {
-      issue(1, (c + 1) * U);
-      __builtin_amdgcn_sched_barrier(0);
-      consume(0, U);
-      __builtin_amdgcn_sched_barrier(0);
-      consume(1, U);
-    } else {
-      consume(0, U);
-    }
-  }
+  pipeline2<U>(nch, issue, consume);
   // remainder: full steps past the last chunk, then the partial step (K % 2048)
   for (int st = nch * U; st < nfull; ++st) {
     const int64_t kb = (int64_t)st << 10;
@@ -245,88 +185,7 @@ __global__ void __launch_bounds__(256) gemv_w4_rows_kernel(const uint16_t* __res
     consume(0, 1);
   }
 
-  // ---- reductions + epilogue
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      const float v = wave_sum(acc[r][m]);
-      if (lane == 0) red[wid * R + r][m] = v;
-    }
-  if (ep.norm) {
-    if (rs_pre) {
-      if (wid == 0) {
-        const int n4 = ep.ssq_tiles >> 2;
-#pragma unroll
-        for (int m = 0; m < (MR <= 2 ? MR : 1); ++m) {
-          float t = 0.f;
-#pragma unroll
-          for (int j = 0; j < SSQ4; ++j)
-            if (lane + j * 64 < n4) t += (ssq_v[m][j][0] + ssq_v[m][j][1]) + (ssq_v[m][j][2] + ssq_v[m][j][3]);
-          t = wave_sum(t);
-          if (lane == 0 && m < M) rstd_s[m] = rsqrtf(t / (float)K + ep.norm_eps);
-        }
-      }
-    } else {
-      skinny_rstd<4>(A, lda, M, K, ep, rstd_s);
-    }
-  }
-  __syncthreads();
-  if (tid < M) {
-    float v[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) v[c] = red[c][tid];
-    if (ep.norm) {
-      const float rs = rstd_s[tid];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) v[c] *= rs;
-    }
-    const bool fast = full16 && !ep.bias_f32 && !ep.act && !ep.out_f32 && ep.out_group == 0 && !ep.table &&
-                      !ep.prelu && !ep.post_act && ep.alpha == 1.f;
-    if (fast) {   // bias / residual from the prologue registers (lane tid < M loaded row tid)
-      if (pre_bias) {
-        float f[8];
-        unpack8(pre_b[0], f);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] += f[q];
-        unpack8(pre_b[1], f);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[8 + q] += f[q];
-      }
-      if (ep.glu) {
-        float g[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) g[q] = v[q] * fast_rcp(1.f + __expf(-v[q])) * v[8 + q];
-        *(u32x4_t*)((uint16_t*)C + (int64_t)tid * ldc + (n0 >> 1)) = pack8(g);
-        return;
-      }
-      if (pre_res) {
-        float f[8];
-        unpack8(pre_r[0], f);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] += f[q];
-        unpack8(pre_r[1], f);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[8 + q] += f[q];
-      }
-      const u32x4_t o0 = pack8(v), o1 = pack8(v + 8);
-      uint16_t* o = (uint16_t*)C + (int64_t)tid * ldc + n0;
-      *(u32x4_t*)o = o0;
-      *(u32x4_t*)(o + 8) = o1;
-      if (ep.ssq_out) {
-        float f[16], t = 0.f;
-        unpack8(o0, f);
-        unpack8(o1, f + 8);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) t += f[q] * f[q];
-        ep.ssq_out[(int64_t)tid * ep.ssq_tiles + (n0 >> 4)] = t;
-      }
-    } else {
-      GemmEpi e2 = ep;
-      e2.norm = 0;   // rstd applied above
-      epi_store16_dec(v, 1.f, tid, n0, M, N, C, ldc, e2);
-    }
-  }
+  row_gemv_tail<MR>(acc, pre, red, rstd_s, NoColScale{}, A, lda, C, ldc, M, N, K, n0, ep);
 }
 
 // ============================================================================ decode, 4 < M <= 32
@@ -470,227 +329,48 @@ __global__ void __launch_bounds__(256) gemm_skinny_w4_kernel(const uint16_t* __r
       for (int r = 0; r < 4; ++r) red[wid][i * 16 + 4 * g + r][t * 16 + col] = acc[i][t][r];
   if (ep.norm) skinny_rstd<NWV>(A, lda, M, K, ep, rstd_s);
   __syncthreads();
-  // wave sum, kept in red[0] (thread-owned elements only: no race)
-  for (int i = tid; i < ROWS * COLS; i += 256) {
-    const int m = i / COLS, c = i - m * COLS;
-    red[0][m][c] = (red[0][m][c] + red[1][m][c]) + (red[2][m][c] + red[3][m][c]);
-  }
-  if (ws != nullptr) {
-    // ---- in-launch split-K: write-through partial slab, ticket, the last split sums in order
-    const int64_t slab = (int64_t)M * N;
-    for (int i = tid; i < M * COLS; i += 256) {
-      const int m = i / COLS, c = i - m * COLS;
-      if (n0 + c < N)
-        __hip_atomic_store(ws + blockIdx.y * slab + (int64_t)m * N + n0 + c, red[0][m][c], __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const uint32_t prev = __hip_atomic_fetch_add(cnt + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool last = prev == gridDim.y - 1;
-      if (last) __hip_atomic_store(cnt + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last_s = last ? 1 : 0;
-    }
-    __syncthreads();
-    if (!last_s) return;
-    const int S = gridDim.y;
-    for (int i = tid; i < M * COLS; i += 256) {
-      const int m = i / COLS, c = i - m * COLS;
-      const float* p = ws + (int64_t)m * N + min(n0 + c, N - 1);
-      float v = 0.f;
-      for (int s0 = 0; s0 < S; s0 += 8) {   // 8 slab loads in flight; summed in split order
-        float pv[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          pv[j] = __hip_atomic_load(p + min(s0 + j, S - 1) * slab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v += s0 + j < S ? pv[j] : 0.f;
-      }
-      red[1][m][c] = v;
-    }
-  }
-  const int src = ws != nullptr ? 1 : 0;
-  __syncthreads();
-  if (tid < M * TPW) {   // thread: (row m, 16-column tile t)
-    const int m = tid / TPW, t = tid - m * TPW;
-    float v[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) v[c] = red[src][m][t * 16 + c];
-    epi_store16_dec(v, rstd_s[m], m, n0 + t * 16, M, N, C, ldc, ep);
-  }
+  if (!splitk_wide<ROWS, COLS>(red, last_s, ws, cnt, M, N, n0)) return;
+  stripe_store<TPW>(red, ws != nullptr ? 1 : 0, rstd_s, NoColScale{}, n0, M, N, C, ldc, ep);
 }
 
 // ============================================================================ prefill
-// gemm_w8_kernel with a 4-bit W tile: per 64-wide k tile a thread loads its W chunks as one
+// gemm_wtile_kernel with a 4-bit W tile: per 64-wide k tile a thread loads its W chunks as one
 // dword of 8 codes plus the chunk's parameter dword, and widens them to 8 bf16 into the
 // swizzled LDS image.  K % 64 == 32 (G = 32 shards): the last tile's upper chunks are zeros.
-template <int BM, int BN, int WM, int WN>
-__global__ void __launch_bounds__(WM* WN * 64)
-gemm_w4_kernel(const uint16_t* __restrict__ A, int64_t lda, const uint8_t* __restrict__ W, int64_t ldw,
-               const uint32_t* __restrict__ P, int64_t ldp, int gshift, void* __restrict__ C, int64_t ldc, int M, int N,
-               int K, GemmEpi ep) {
-  constexpr int NT = WM * WN * 64;
-  constexpr int TM = BM / WM, TN = BN / WN;
-  constexpr int MR = TM / 16, NR = TN / 16;
-  constexpr int CA = BM * 8 / NT;  // 8-element chunks per thread
-  constexpr int CB = BN * 8 / NT;
-  static_assert(CA >= 1 && CB >= 1 && BM * 8 % NT == 0 && BN * 8 % NT == 0, "bad tiling");
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* sA = smem;                 // [2][BM][128 B] bf16
-  char* sB = smem + 2 * BM * 128;  // [2][BN][128 B] bf16 (widened from 4-bit codes)
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid / WN, wn = wid % WN;
-  const int tiles_n = (N + BN - 1) / BN, tiles_m = (M + BM - 1) / BM;
-  const int bid = xcd_remap(blockIdx.x, tiles_n * tiles_m);
-  const int m0 = (bid / tiles_n) * BM, n0 = (bid % tiles_n) * BN;
-
-  const uint16_t* pa[CA];
-  const uint8_t* pb[CB];
-  const uint32_t* pq[CB];
-  int la[CA], lb[CB];
-  // chunk column (the same for every chunk of a thread: NT % 8 == 0)
-  const int cc8 = (tid & 7) * 8;
-#pragma unroll
-  for (int i = 0; i < CA; ++i) {
-    const int id = tid + i * NT, r = id >> 3, c = id & 7;
-    pa[i] = A + (int64_t)min(m0 + r, M - 1) * lda + c * 8;
-    la[i] = swz(r, c);
-  }
-#pragma unroll
-  for (int i = 0; i < CB; ++i) {
-    const int id = tid + i * NT, r = id >> 3, c = id & 7;
-    const int64_t row = min(n0 + r, N - 1);
-    pb[i] = W + row * ldw + c * 4;
-    pq[i] = P + row * ldp;
-    lb[i] = swz(r, c);
-  }
-  f32x4_t acc[MR][NR];
-#pragma unroll
-  for (int i = 0; i < MR; ++i)
-#pragma unroll
-    for (int j = 0; j < NR; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-  u32x4_t ra[CA];
-  uint32_t rb[CB], rp[CB];
-  const int nk = (K + 63) / 64;
-  auto load_tile = [&](const int kt) {
-    const int k = kt * 64 + cc8;
-    const bool ok = k < K;
-    const int kc = ok ? k : 0;                 // clamped (in-row) address, values zeroed
-#pragma unroll
-    for (int i = 0; i < CA; ++i) {
-      const u32x4_t a = *(const u32x4_t*)(pa[i] + (kc - cc8));
-      ra[i] = ok ? a : (u32x4_t){0u, 0u, 0u, 0u};
-    }
-#pragma unroll
-    for (int i = 0; i < CB; ++i) {
-      rb[i] = *(const uint32_t*)(pb[i] + ((kc - cc8) >> 1));
-      rp[i] = pq[i][kc >> gshift];
-    }
+struct W4Tile {
+  typedef uint32_t param_t;
+  struct chunk_t {
+    uint32_t w, p;
   };
-  auto store_tile = [&](char* dA, char* dB) {
-#pragma unroll
-    for (int i = 0; i < CA; ++i) *(u32x4_t*)(dA + la[i]) = ra[i];
-#pragma unroll
-    for (int i = 0; i < CB; ++i) *(u32x4_t*)(dB + lb[i]) = w4x8_to_bf16(rb[i], h2f_lo(rp[i]), h2f_hi(rp[i]));
+  struct src_t {
+    const uint8_t* w;
+    const uint32_t* p;
+    int cc8;   // the chunk's first k inside a tile
   };
-  load_tile(0);
-  store_tile(sA, sB);
-  __syncthreads();
-  const int frow = lane & 15, fq = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) load_tile(kt + 1);
-    const char* tA = sA + cur * BM * 128;
-    const char* tB = sB + cur * BN * 128;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      bf16x8_t fa[MR], fb[NR];
-#pragma unroll
-      for (int i = 0; i < MR; ++i) fa[i] = *(const bf16x8_t*)(tA + swz(wm * TM + i * 16 + frow, s * 4 + fq));
-#pragma unroll
-      for (int j = 0; j < NR; ++j) fb[j] = *(const bf16x8_t*)(tB + swz(wn * TN + j * 16 + frow, s * 4 + fq));
-#pragma unroll
-      for (int i = 0; i < MR; ++i)
-#pragma unroll
-        for (int j = 0; j < NR; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    if (kt + 1 < nk) store_tile(sA + (cur ^ 1) * BM * 128, sB + (cur ^ 1) * BN * 128);
-    __syncthreads();
+  static constexpr bool KTAIL = true, COLSCALE = false;
+  const uint8_t* W;
+  int64_t ldw;
+  const uint32_t* P;
+  int64_t ldp;
+  int gshift;
+  __device__ __forceinline__ W4Tile(const uint8_t* W_, int64_t ldw_, const uint32_t* P_, int64_t ldp_, int gshift_)
+      : W(W_), ldw(ldw_), P(P_), ldp(ldp_), gshift(gshift_) {}
+  __device__ __forceinline__ src_t src(const int64_t n, const int c) const {
+    return src_t{W + n * ldw + c * 4, P + n * ldp, c * 8};
   }
-  // epilogue through LDS, 16-row slabs
-  constexpr int LDSTR = TN + 4;
-  float* es = (float*)smem + wid * 16 * LDSTR;
-  constexpr int LPR = TN / 16;
-  constexpr int RPP = 64 / LPR;
-  constexpr int NPASS = RPP >= 16 ? 1 : 16 / RPP;
-  Unroll<0, MR>::run([&](const int i) {
-#pragma unroll
-    for (int j = 0; j < NR; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) es[(fq * 4 + r) * LDSTR + j * 16 + frow] = acc[i][j][r];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int p = 0; p < NPASS; ++p) {
-      const int rr = p * RPP + lane / LPR;
-      const int cc = (lane % LPR) * 16;
-      if (rr < 16) {
-        const int n = n0 + wn * TN + cc;
-        float v[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4_t t = *(const f32x4_t*)(es + rr * LDSTR + cc + q * 4);
-          v[q * 4 + 0] = t[0]; v[q * 4 + 1] = t[1]; v[q * 4 + 2] = t[2]; v[q * 4 + 3] = t[3];
-        }
-        epi_store16(v, m0 + wm * TM + i * 16 + rr, n, M, N, C, ldc, ep);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  });
-}
-
-template <int BM, int BN, int WM, int WN>
-static hipError_t launch_w4(const uint16_t* A, int64_t lda, const uint8_t* W, int64_t ldw, const uint32_t* P,
-                            int64_t ldp, int gshift, void* C, int64_t ldc, int M, int N, int K, const GemmEpi& ep,
-                            hipStream_t stream) {
-  const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  size_t lds = 2 * (size_t)(BM + BN) * 128;
-  const size_t epi = (size_t)WM * WN * 16 * (BN / WN + 4) * 4;
-  if (epi > lds) lds = epi;
-  auto kern = gemm_w4_kernel<BM, BN, WM, WN>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
+  __device__ __forceinline__ chunk_t load(const src_t& s, const int koff) const {
+    return chunk_t{*(const uint32_t*)(s.w + (koff >> 1)), s.p[(koff + s.cc8) >> gshift]};
   }
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(WM * WN * 64), lds, stream, A, lda, W, ldw, P, ldp, gshift, C, ldc, M, N,
-                     K, ep);
-  return hipGetLastError();
-}
+  static __device__ __forceinline__ u32x4_t widen(const chunk_t c) { return w4x8_to_bf16(c.w, h2f_lo(c.p), h2f_hi(c.p)); }
+};
 
 // Decode plan for 4-bit weights, 4 < M <= 32 (M <= 4 runs the unsplit row-streaming GEMV):
 // column stripes of 64 / 32 / 16 (N divisibility; at most 32 for two row tiles), K split so that
 // stripes x splits reach ~512 workgroups (2 per CU), every split >= 4 k blocks of 128 (one per
 // wave), chunks whole 128-wide blocks.
-W8DecPlan w4_dec_plan(int M, int N, int K) {
-  W8DecPlan p{};
-  p.tpw = 1;
-  p.ks = 1;
-  p.kchunk = K;
-  if (M <= 4 || M > 32) return p;
-  p.tpw = N % 64 == 0 && M <= 16 ? 4 : (N % 32 == 0 ? 2 : 1);
-  const int stripes = (N + 16 * p.tpw - 1) / (16 * p.tpw);
-  int ks = (512 + stripes - 1) / stripes;
-  const int kmax = K / 512 > 1 ? K / 512 : 1;
-  ks = ks < kmax ? ks : kmax;
-  int kchunk = (K + ks - 1) / ks;
-  kchunk = (kchunk + 127) / 128 * 128;
-  p.kchunk = kchunk;
-  p.ks = (K + kchunk - 1) / kchunk;
-  if (p.ks == 1) p.kchunk = K;
-  return p;
+DecPlan w4_dec_plan(int M, int N, int K) {
+  if (M <= 4 || M > 32) return DecPlan{1, 1, K};
+  return dec_plan_stripes(N, K, N % 64 == 0 && M <= 16 ? 4 : (N % 32 == 0 ? 2 : 1), 128, 512);
 }
 
 hipError_t gemm_w4(const uint16_t* A, int64_t lda, const uint8_t* W4, int64_t ldw, const uint32_t* params, int G,
@@ -711,7 +391,7 @@ hipError_t gemm_w4(const uint16_t* A, int64_t lda, const uint8_t* W4, int64_t ld
     return hipGetLastError();
   }
   if (M <= 32) {
-    const W8DecPlan pl = w4_dec_plan(M, N, K);
+    const DecPlan pl = w4_dec_plan(M, N, K);
     if (pl.ks > 1 && pl.ks != ksplit) return hipErrorInvalidValue;   // host sized ws / counters for its plan
     const int gy = pl.ks;
     if (gy > 1 && (ws == nullptr || cnt == nullptr)) return hipErrorInvalidValue;
@@ -739,8 +419,8 @@ hipError_t gemm_w4(const uint16_t* A, int64_t lda, const uint8_t* W4, int64_t ld
   }
   const int64_t t128 = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
   if (t128 >= 256)
-    return launch_w4<128, 128, 2, 2>(A, lda, W4, ldw, params, ldp, gshift, C, ldc, M, N, K, ep, stream);
-  return launch_w4<64, 64, 2, 2>(A, lda, W4, ldw, params, ldp, gshift, C, ldc, M, N, K, ep, stream);
+    return launch_wtile<128, 128, 2, 2, W4Tile>(A, lda, W4, ldw, params, ldp, gshift, C, ldc, M, N, K, ep, stream);
+  return launch_wtile<64, 64, 2, 2, W4Tile>(A, lda, W4, ldw, params, ldp, gshift, C, ldc, M, N, K, ep, stream);
 }
 
 }  // namespace lumen

@@ -123,6 +123,40 @@ void check_bf16_rows(const at::Tensor& t, const char* name) {
               name, " rows must be 16-byte aligned");
 }
 
+// Optional bias ([>= N] contiguous, fp32 or bf16) and residual (bf16 rows, indexed by output row) of
+// a GEMM epilogue; op prefixes the error messages.
+void epi_bias_residual(lumen::GemmEpi& ep, const char* op, int64_t N, const c10::optional<at::Tensor>& bias,
+                       const c10::optional<at::Tensor>& residual) {
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->numel() >= N && bias->is_contiguous(), op, ": bias");
+    TORCH_CHECK(bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16, op, ": bias dtype");
+    ep.bias = bias->data_ptr();
+    ep.bias_f32 = bias->scalar_type() == at::kFloat;
+  }
+  if (residual.has_value() && residual->defined()) {
+    check_bf16_rows(*residual, "residual");
+    ep.residual = bf(*residual);
+    ep.ldr = residual->stride(0);
+  }
+}
+
+// Split-K workspace of a decode GEMM whose plan has ks splits: per-split fp32 slabs (no zero-fill)
+// and the per-tile arrival counters; both null when the plan does not split.
+struct SplitKBufs {
+  at::Tensor slabs;
+  float* ws = nullptr;
+  uint32_t* cnt = nullptr;
+};
+SplitKBufs splitk_bufs(const at::Tensor& a, int ks, int64_t M, int64_t N) {
+  SplitKBufs b;
+  if (ks > 1) {
+    b.slabs = at::empty({ks, M, N}, a.options().dtype(at::kFloat));
+    b.ws = b.slabs.data_ptr<float>();
+    b.cnt = splitk_counters(a, (N + 15) / 16);
+  }
+  return b;
+}
+
 // ---------------------------------------------------------------- gemm
 void gemm(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
           const c10::optional<at::Tensor>& residual, const c10::optional<at::Tensor>& table,
@@ -146,17 +180,7 @@ void gemm(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tens
   lumen::GemmEpi ep{};
   ep.alpha = (float)alpha;
   ep.act = (int)act;
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->numel() >= N && bias->is_contiguous(), "gemm: bias");
-    TORCH_CHECK(bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16, "gemm: bias dtype");
-    ep.bias = bias->data_ptr();
-    ep.bias_f32 = bias->scalar_type() == at::kFloat;
-  }
-  if (residual.has_value() && residual->defined()) {
-    check_bf16_rows(*residual, "residual");
-    ep.residual = bf(*residual);
-    ep.ldr = residual->stride(0);
-  }
+  epi_bias_residual(ep, "gemm", N, bias, residual);
   if (table.has_value() && table->defined()) {
     check_bf16_rows(*table, "table");
     TORCH_CHECK(table_period > 0, "gemm: table_period");
@@ -180,12 +204,9 @@ void gemm(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tens
   // decode-shaped GEMMs (M <= 32): bandwidth-bound split-K kernel (tile -1 = auto, 9 = force)
   if ((tile == -1 || tile == 9) && M <= 32 && M > 0) {
     const int ks = lumen::skinny_ksplit((int)N, (int)K);
-    at::Tensor ws;
-    if (ks > 1) ws = at::empty({ks, M, N}, a.options().dtype(at::kFloat));   // per-split slabs, no zero-fill
-    uint32_t* cnt = ks > 1 ? splitk_counters(a, (N + 15) / 16) : nullptr;
+    const SplitKBufs sk = splitk_bufs(a, ks, M, N);
     LM_CHECK_HIP(lumen::gemm_skinny(bf(a), a.stride(0), bf(w), w.stride(0), out.data_ptr(), out.stride(0), (int)M,
-                                       (int)N, (int)K, ep, ks > 1 ? ws.data_ptr<float>() : nullptr, cnt, ks,
-                                       cur_stream()));
+                                       (int)N, (int)K, ep, sk.ws, sk.cnt, ks, cur_stream()));
     return;
   }
   LM_CHECK_HIP(lumen::gemm_bf16(bf(a), a.stride(0), bf(w), w.stride(0), out.data_ptr(), out.stride(0),
@@ -265,31 +286,13 @@ void gemm_w8(const at::Tensor& a, const at::Tensor& w8, const at::Tensor& scale,
   ep.act = (int)act;
   ep.glu = (int)glu;
   ep.out_f32 = out.scalar_type() == at::kFloat;
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->numel() >= N && bias->is_contiguous() &&
-                (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16), "gemm_w8: bias");
-    ep.bias = bias->data_ptr();
-    ep.bias_f32 = bias->scalar_type() == at::kFloat;
-  }
-  if (residual.has_value() && residual->defined()) {
-    check_bf16_rows(*residual, "residual");
-    ep.residual = bf(*residual);
-    ep.ldr = residual->stride(0);
-  }
+  epi_bias_residual(ep, "gemm_w8", N, bias, residual);
   const at::DeviceGuard guard(a.device());
-  int ks = 1;
-  at::Tensor ws;
-  uint32_t* cnt = nullptr;
-  if (M <= 32) {
-    ks = lumen::w8_dec_plan((int)M, (int)N, (int)K).ks;
-    if (ks > 1) {
-      ws = at::empty({ks, M, N}, a.options().dtype(at::kFloat));
-      cnt = splitk_counters(a, (N + 15) / 16);
-    }
-  }
+  const int ks = M <= 32 ? lumen::w8_dec_plan((int)M, (int)N, (int)K).ks : 1;
+  const SplitKBufs sk = splitk_bufs(a, ks, M, N);
   LM_CHECK_HIP(lumen::gemm_w8(bf(a), a.stride(0), reinterpret_cast<const uint8_t*>(w8.data_ptr()), w8.stride(0),
                                  scale.data_ptr<float>(), out.data_ptr(), out.stride(0), (int)M, (int)N, (int)K, ep,
-                                 ks > 1 ? ws.data_ptr<float>() : nullptr, cnt, ks, cur_stream()));
+                                 sk.ws, sk.cnt, ks, cur_stream()));
 }
 
 // ---------------------------------------------------------------- 4-bit group-quantised weight GEMM
@@ -326,32 +329,13 @@ void gemm_w4(const at::Tensor& a, const at::Tensor& w4, const at::Tensor& params
   ep.act = (int)act;
   ep.glu = (int)glu;
   ep.out_f32 = out.scalar_type() == at::kFloat;
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->numel() >= N && bias->is_contiguous() &&
-                (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16), "gemm_w4: bias");
-    ep.bias = bias->data_ptr();
-    ep.bias_f32 = bias->scalar_type() == at::kFloat;
-  }
-  if (residual.has_value() && residual->defined()) {
-    check_bf16_rows(*residual, "residual");
-    ep.residual = bf(*residual);
-    ep.ldr = residual->stride(0);
-  }
+  epi_bias_residual(ep, "gemm_w4", N, bias, residual);
   const at::DeviceGuard guard(a.device());
-  int ks = 1;
-  at::Tensor ws;
-  uint32_t* cnt = nullptr;
-  if (M <= 32) {
-    ks = lumen::w4_dec_plan((int)M, (int)N, (int)K).ks;
-    if (ks > 1) {
-      ws = at::empty({ks, M, N}, a.options().dtype(at::kFloat));
-      cnt = splitk_counters(a, (N + 15) / 16);
-    }
-  }
+  const int ks = M <= 32 ? lumen::w4_dec_plan((int)M, (int)N, (int)K).ks : 1;
+  const SplitKBufs sk = splitk_bufs(a, ks, M, N);
   LM_CHECK_HIP(lumen::gemm_w4(bf(a), a.stride(0), w4.data_ptr<uint8_t>(), w4.stride(0),
                                  reinterpret_cast<const uint32_t*>(params.data_ptr()), (int)G, out.data_ptr(),
-                                 out.stride(0), (int)M, (int)N, (int)K, ep, ks > 1 ? ws.data_ptr<float>() : nullptr, cnt,
-                                 ks, cur_stream()));
+                                 out.stride(0), (int)M, (int)N, (int)K, ep, sk.ws, sk.cnt, ks, cur_stream()));
 }
 
 // ---------------------------------------------------------------- decode GEMM (norm folding)
@@ -398,42 +382,29 @@ void gemm_dec(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::
     ep.ssq_out = ssq_out->data_ptr<float>();
     ep.ssq_tiles = (int)ssq_out->size(1);
   }
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->numel() >= N && bias->is_contiguous() &&
-                (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16), "gemm_dec: bias");
-    ep.bias = bias->data_ptr();
-    ep.bias_f32 = bias->scalar_type() == at::kFloat;
-  }
-  if (residual.has_value() && residual->defined()) {
-    check_bf16_rows(*residual, "residual");
-    ep.residual = bf(*residual);
-    ep.ldr = residual->stride(0);
-  }
+  epi_bias_residual(ep, "gemm_dec", N, bias, residual);
   const at::DeviceGuard guard(a.device());
   const bool is_f8 = w.scalar_type() == at::kFloat8_e4m3fn;
   const int ks = is_w4 ? lumen::w4_dec_plan((int)M, (int)N, (int)K).ks
                  : is_f8 ? lumen::w8_dec_plan((int)M, (int)N, (int)K).ks : lumen::skinny_ksplit((int)N, (int)K);
-  at::Tensor ws;
-  if (ks > 1) ws = at::empty({ks, M, N}, a.options().dtype(at::kFloat));
-  uint32_t* cnt = ks > 1 ? splitk_counters(a, (N + 15) / 16) : nullptr;
-  float* wsp = ks > 1 ? ws.data_ptr<float>() : nullptr;
+  const SplitKBufs sk = splitk_bufs(a, ks, M, N);
   if (is_w4) {
     TORCH_CHECK(scale.has_value() && scale->defined(), "gemm_dec: 4-bit weights need params float16 [N, K / G, 2]");
     const int64_t G = check_w4(w, *scale, K, "gemm_dec");
     LM_CHECK_HIP(lumen::gemm_w4(bf(a), a.stride(0), w.data_ptr<uint8_t>(), w.stride(0),
                                    reinterpret_cast<const uint32_t*>(scale->data_ptr()), (int)G, out.data_ptr(),
-                                   out.stride(0), (int)M, (int)N, (int)K, ep, wsp, cnt, ks, cur_stream()));
+                                   out.stride(0), (int)M, (int)N, (int)K, ep, sk.ws, sk.cnt, ks, cur_stream()));
   } else if (w.scalar_type() == at::kFloat8_e4m3fn) {
     TORCH_CHECK(scale.has_value() && scale->defined() && scale->scalar_type() == at::kFloat && scale->numel() == N,
                 "gemm_dec: fp8 weights need scale f32 [N]");
     TORCH_CHECK(K % 64 == 0 && w.stride(0) % 16 == 0, "gemm_dec: fp8 K % 64");
     LM_CHECK_HIP(lumen::gemm_w8(bf(a), a.stride(0), reinterpret_cast<const uint8_t*>(w.data_ptr()), w.stride(0),
                                    scale->data_ptr<float>(), out.data_ptr(), out.stride(0), (int)M, (int)N, (int)K, ep,
-                                   wsp, cnt, ks, cur_stream()));
+                                   sk.ws, sk.cnt, ks, cur_stream()));
   } else {
     TORCH_CHECK(w.scalar_type() == at::kBFloat16 && K % 32 == 0, "gemm_dec: bf16 weights, K % 32");
     LM_CHECK_HIP(lumen::gemm_skinny(bf(a), a.stride(0), bf(w), w.stride(0), out.data_ptr(), out.stride(0), (int)M,
-                                       (int)N, (int)K, ep, wsp, cnt, ks, cur_stream()));
+                                       (int)N, (int)K, ep, sk.ws, sk.cnt, ks, cur_stream()));
   }
 }
 
@@ -466,17 +437,7 @@ void gemm_f8(const at::Tensor& a8, const at::Tensor& sa, const at::Tensor& w8, c
   ep.alpha = 1.f;
   ep.glu = (int)glu;
   ep.out_f32 = out.scalar_type() == at::kFloat;
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->numel() >= N && bias->is_contiguous() &&
-                (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16), "gemm_f8: bias");
-    ep.bias = bias->data_ptr();
-    ep.bias_f32 = bias->scalar_type() == at::kFloat;
-  }
-  if (residual.has_value() && residual->defined()) {
-    check_bf16_rows(*residual, "residual");
-    ep.residual = bf(*residual);
-    ep.ldr = residual->stride(0);
-  }
+  epi_bias_residual(ep, "gemm_f8", N, bias, residual);
   const at::DeviceGuard guard(a8.device());
   LM_CHECK_HIP(lumen::gemm_f8(reinterpret_cast<const uint8_t*>(a8.data_ptr()), a8.stride(0), sa.data_ptr<float>(),
                                  reinterpret_cast<const uint8_t*>(w8.data_ptr()), w8.stride(0), sw.data_ptr<float>(),
@@ -546,18 +507,8 @@ void gemm_mx(const at::Tensor& a8, const at::Tensor& a_bs, const at::Tensor& w8,
     ep.row_aff = row_aff->data_ptr<float>();
     ep.col_aff = col_aff->data_ptr<float>();
   }
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->numel() >= N && bias->is_contiguous() &&
-                (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16), "gemm_mx: bias");
-    ep.bias = bias->data_ptr();
-    ep.bias_f32 = bias->scalar_type() == at::kFloat;
-  }
-  if (residual.has_value() && residual->defined()) {
-    TORCH_CHECK(!glu, "gemm_mx: residual with glu");
-    check_bf16_rows(*residual, "residual");
-    ep.residual = bf(*residual);
-    ep.ldr = residual->stride(0);
-  }
+  TORCH_CHECK(!glu || !(residual.has_value() && residual->defined()), "gemm_mx: residual with glu");
+  epi_bias_residual(ep, "gemm_mx", N, bias, residual);
   if (ssq_in.has_value() && ssq_in->defined()) {
     check_f32_rows(*ssq_in, M, K / 128, "gemm_mx: ssq_in");
     TORCH_CHECK(ssq_in->size(1) == K / 128 && ssq_in->is_contiguous(), "gemm_mx: ssq_in [M, K/128] contiguous");

@@ -45,6 +45,29 @@ def test_gemm_w8_swiglu(M):
     assert got.shape == (M, I) and _rel(got, ref) < 1e-2
 
 
+# (M, N, K): the row-streaming GEMV (a row shorter than a k step; a full step plus a tail), the MFMA
+# GEMV (one column tile per wave; four with a 19-way K split), the 16-column kernel (7 and 2 K
+# splits) and the 64x64 prefill tile (ragged M); N no multiple of 64
+@pytest.mark.parametrize("M,N,K", [(1, 64, 896), (3, 48, 1088), (5, 80, 896), (16, 64, 4864), (17, 48, 4864),
+                                   (32, 64, 1024), (33, 96, 896), (200, 192, 1024)])
+def test_gemm_w8_exact_integers(M, N, K):
+    """Integer weights in [-8, 8] (exact in e4m3), power-of-two row scales and small integer
+    activations: every product and partial sum is exactly representable (|value| < 2^24), so the
+    fp32 output equals the CPU reference bit for bit whatever the summation order -- any k-order,
+    fragment, column-scale or split-K mix-up shows."""
+    g = torch.Generator().manual_seed(M * 7 + N + K)
+    w = torch.randint(-8, 9, (N, K), generator=g).float()
+    w8 = w.to(torch.float8_e4m3fn)
+    assert torch.equal(w8.float(), w)
+    scale = torch.tensor([0.25, 0.5, 1.0, 2.0])[torch.randint(0, 4, (N,), generator=g)]
+    x = torch.randint(-4, 5, (M, K), generator=g).bfloat16()
+    ref = ops.linear(x.float(), w8, w_scale=scale)
+    assert torch.equal(ref, ((x.double() @ w.double().t()) * scale.double()).float())
+    got = ops.linear(x.to(DEV), w8.to(DEV), w_scale=scale.to(DEV), out_dtype=torch.float32)
+    assert got.dtype == torch.float32
+    torch.testing.assert_close(got.cpu(), ref, rtol=0, atol=0)
+
+
 def test_llm_fp8_matches_cpu_reference():
     cfg = LLM_PRESETS["tiny"]
     cpu = LLM(cfg, dtype=torch.float32, device="cpu")
