@@ -27,6 +27,11 @@ struct RopeKVArgs {
   uint16_t* v_cache;
   int T, H, Hkv, D;
   int kv_fp8;             // caches hold OCP e4m3fn bytes (unit scale, saturated) instead of bf16
+  // per-head q / k RMSNorm before the rotation (Qwen3): y = x * rsqrt(mean(x^2) + eps) * gamma over
+  // each head's D elements in fp32, one bf16 rounding after the rotation.  D = 32 / 64 / 128.
+  const float* q_gamma;   // [D] shared by all q heads (null = no norm; then k_gamma is null too)
+  const float* k_gamma;   // [D] shared by all k heads
+  float eps;
 };
 hipError_t rope_kv(const RopeKVArgs& a, hipStream_t stream);
 

@@ -1,9 +1,11 @@
-// Decoder-LLM kernels for the VLM (Qwen2 / Llama family):
+// Decoder-LLM kernels for the VLM (Qwen2 / Qwen3 / Llama family):
 //
 //  * rope_kv: rotary embedding (rotate-half, HF convention) applied in place to
 //    the q and k heads of the packed QKV projection, fused with the paged KV
 //    cache write (k token-major, v transposed; layouts in llm.h).  Prefill
-//    attention then reads q/k/v straight from the rotated QKV buffer.
+//    attention then reads q/k/v straight from the rotated QKV buffer.  Qwen3:
+//    every q / k head first passes through an RMSNorm over the head dim
+//    (template flag NORM of both kernel forms).
 //  * paged_decode: flash-decoding over the paged cache.  One workgroup per
 //    (split, kv-head, sequence); the G = H / Hkv query heads sharing a kv head
 //    are the 16 MFMA columns, each wave walks its own 64-token blocks with an
@@ -34,6 +36,14 @@ namespace lumen {
 // rotation pair / V element per thread, so a decode step (T = 1..16) spreads over 14+
 // workgroups per token instead of looping 10x inside one (each pass of that loop paid a
 // dependent global round trip: 8 us per layer per token, measured)
+//
+// NORM (per-head q / k RMSNorm, llm.h): a head's D/2 pairs are 16, 32 or 64 consecutive threads,
+// a segment aligned inside one wave (256 is a multiple of D/2), so the head's sum of squares is a
+// xor-butterfly over the segment.  The bound below cuts at a head boundary: a segment is wholly
+// in or wholly out, and the threads past it leave only after the butterfly.
+__device__ __forceinline__ float qk_rstd(float ssq, int D, float eps) { return rsqrtf(ssq / (float)D + eps); }
+
+template <bool NORM>
 __global__ void __launch_bounds__(256) rope_kv_kernel(RopeKVArgs a, int nrot_blocks) {
   const int t = blockIdx.x;
   const int half = a.D >> 1;
@@ -42,13 +52,27 @@ __global__ void __launch_bounds__(256) rope_kv_kernel(RopeKVArgs a, int nrot_blo
   const int64_t blk = slot >= 0 ? (slot >> 6) : 0;
   const int off = (int)(slot & 63);
   if ((int)blockIdx.y < nrot_blocks) {
-    const int idx = blockIdx.y * 256 + threadIdx.x;
-    if (idx >= (a.H + a.Hkv) * half) return;
+    int idx = blockIdx.y * 256 + threadIdx.x;
+    const bool live = idx < (a.H + a.Hkv) * half;
+    if constexpr (NORM) {
+      if (!live) idx = 0;   // reads head 0 again, stores nothing
+    } else {
+      if (!live) return;
+    }
     const int p = a.pos[t];
     const float2* cs = reinterpret_cast<const float2*>(a.cos_sin) + (int64_t)p * half;
     const int hh = idx / half, i = idx - hh * half;
     uint16_t* hp = row + hh * a.D;
-    const float x1 = bf2f(hp[i]), x2 = bf2f(hp[i + half]);
+    float x1 = bf2f(hp[i]), x2 = bf2f(hp[i + half]);
+    if constexpr (NORM) {
+      float ssq = x1 * x1 + x2 * x2;
+      for (int m = 1; m < half; m <<= 1) ssq += __shfl_xor(ssq, m, 64);
+      const float rstd = qk_rstd(ssq, a.D, a.eps);
+      const float* gm = hh < a.H ? a.q_gamma : a.k_gamma;
+      x1 = x1 * rstd * gm[i];
+      x2 = x2 * rstd * gm[i + half];
+      if (!live) return;
+    }
     const float2 c = cs[i];
     const float y1 = x1 * c.x - x2 * c.y, y2 = x2 * c.x + x1 * c.y;
     const uint16_t b1 = f2bf(y1), b2 = f2bf(y2);
@@ -83,7 +107,9 @@ __global__ void __launch_bounds__(256) rope_kv_kernel(RopeKVArgs a, int nrot_blo
 // k cache rows; v heads: the [64 x D] tile goes through LDS and leaves d-major, 8 tokens (16 or
 // 8 bytes) per store when their slots are consecutive in one block.  The per-element kernel above
 // wrote V with 2-byte stores 128 bytes apart (11 us per 8B-prefill layer at 624 tokens).
-template <int D>
+// NORM: the 4 adjacent threads of a (token, head) each sum the D/4 squares of the values they hold;
+// two xor steps over the quad give the head's sum (a quad leaves together at the ragged last tile).
+template <int D, bool NORM>
 __global__ void __launch_bounds__(256) rope_kv_tile_kernel(RopeKVArgs a) {
   constexpr int HALF = D / 2, PPT = D / 8;       // rotation pairs per thread
   __shared__ __attribute__((aligned(16))) uint16_t vt[64][D + 8];
@@ -94,12 +120,48 @@ __global__ void __launch_bounds__(256) rope_kv_tile_kernel(RopeKVArgs a) {
     if (t >= a.T) return;
     uint16_t* hp = a.qkv + (int64_t)t * a.ld + hh * D;
     const float2* cs = reinterpret_cast<const float2*>(a.cos_sin) + (int64_t)a.pos[t] * HALF + c0;
+    u32x4_t raw1[PPT / 8], raw2[PPT / 8];   // NORM: the thread's values, held across the reduction
+    float g1[PPT], g2[PPT];                 // NORM: gamma of each element, 16-byte loads
+    float rstd = 1.f;
+    if constexpr (NORM) {
+      float ssq = 0.f;
+#pragma unroll
+      for (int u = 0; u < PPT; u += 8) {
+        float x1[8], x2[8];
+        raw1[u / 8] = *(const u32x4_t*)(hp + c0 + u);
+        raw2[u / 8] = *(const u32x4_t*)(hp + HALF + c0 + u);
+        unpack8(raw1[u / 8], x1);
+        unpack8(raw2[u / 8], x2);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) ssq += x1[q] * x1[q] + x2[q] * x2[q];
+      }
+      const float* gm = (hh < a.H ? a.q_gamma : a.k_gamma) + c0;
+#pragma unroll
+      for (int u = 0; u < PPT; u += 4) {
+        const float4 ga = *(const float4*)(gm + u), gb = *(const float4*)(gm + HALF + u);
+        g1[u] = ga.x; g1[u + 1] = ga.y; g1[u + 2] = ga.z; g1[u + 3] = ga.w;
+        g2[u] = gb.x; g2[u + 1] = gb.y; g2[u + 2] = gb.z; g2[u + 3] = gb.w;
+      }
+      ssq += __shfl_xor(ssq, 1, 64);
+      ssq += __shfl_xor(ssq, 2, 64);
+      rstd = qk_rstd(ssq, D, a.eps);
+    }
     float y1[PPT], y2[PPT];
 #pragma unroll
     for (int u = 0; u < PPT; u += 8) {
       float x1[8], x2[8];
-      unpack8(*(const u32x4_t*)(hp + c0 + u), x1);
-      unpack8(*(const u32x4_t*)(hp + HALF + c0 + u), x2);
+      if constexpr (NORM) {
+        unpack8(raw1[u / 8], x1);
+        unpack8(raw2[u / 8], x2);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          x1[q] = x1[q] * rstd * g1[u + q];
+          x2[q] = x2[q] * rstd * g2[u + q];
+        }
+      } else {
+        unpack8(*(const u32x4_t*)(hp + c0 + u), x1);
+        unpack8(*(const u32x4_t*)(hp + HALF + c0 + u), x2);
+      }
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const float2 c = cs[u + q];
@@ -168,15 +230,25 @@ __global__ void __launch_bounds__(256) rope_kv_tile_kernel(RopeKVArgs a) {
 
 hipError_t rope_kv(const RopeKVArgs& a, hipStream_t stream) {
   if (a.T == 0) return hipSuccess;
+  const bool norm = a.q_gamma != nullptr;
+  // the norm's segmented butterfly needs a power-of-two D/2 that divides the wave
+  if (norm && (a.k_gamma == nullptr || !(a.D == 32 || a.D == 64 || a.D == 128))) return hipErrorInvalidValue;
   if (a.T >= 64 && (a.D == 64 || a.D == 128) && a.ld % 8 == 0) {
     const dim3 grid((a.T + 63) / 64, a.H + 2 * a.Hkv);
-    if (a.D == 128) hipLaunchKernelGGL(rope_kv_tile_kernel<128>, grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(rope_kv_tile_kernel<64>, grid, dim3(256), 0, stream, a);
+    if (a.D == 128) {
+      if (norm) hipLaunchKernelGGL((rope_kv_tile_kernel<128, true>), grid, dim3(256), 0, stream, a);
+      else hipLaunchKernelGGL((rope_kv_tile_kernel<128, false>), grid, dim3(256), 0, stream, a);
+    } else {
+      if (norm) hipLaunchKernelGGL((rope_kv_tile_kernel<64, true>), grid, dim3(256), 0, stream, a);
+      else hipLaunchKernelGGL((rope_kv_tile_kernel<64, false>), grid, dim3(256), 0, stream, a);
+    }
     return hipGetLastError();
   }
   const int nrot_blocks = ((a.H + a.Hkv) * (a.D / 2) + 255) / 256;
   const int v_blocks = a.slots ? (a.Hkv * a.D + 255) / 256 : 0;
-  hipLaunchKernelGGL(rope_kv_kernel, dim3(a.T, nrot_blocks + v_blocks), dim3(256), 0, stream, a, nrot_blocks);
+  const dim3 grid(a.T, nrot_blocks + v_blocks);
+  if (norm) hipLaunchKernelGGL(rope_kv_kernel<true>, grid, dim3(256), 0, stream, a, nrot_blocks);
+  else hipLaunchKernelGGL(rope_kv_kernel<false>, grid, dim3(256), 0, stream, a, nrot_blocks);
   return hipGetLastError();
 }
 

@@ -39,10 +39,28 @@ int check_cache(const at::Tensor& kc, const at::Tensor& vc, int64_t Hkv, int64_t
   return f8 ? 1 : 0;
 }
 
+// per-head q / k RMSNorm weights (Qwen3): both or neither, f32 [D], 16-byte aligned; returns true when given
+bool check_qk_norm(const c10::optional<at::Tensor>& qg, const c10::optional<at::Tensor>& kg, double eps, int64_t D,
+                   const at::Tensor& like, const float** q_gamma, const float** k_gamma) {
+  const bool hq = qg.has_value() && qg->defined(), hk = kg.has_value() && kg->defined();
+  TORCH_CHECK(hq == hk, "qk norm: q_gamma and k_gamma come together");
+  if (!hq) return false;
+  TORCH_CHECK(D == 32 || D == 64 || D == 128, "qk norm: head dim 32, 64 or 128");
+  TORCH_CHECK(eps > 0, "qk norm: eps > 0");
+  for (const at::Tensor* t : {&*qg, &*kg})
+    TORCH_CHECK(t->is_cuda() && t->device() == like.device() && t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                t->numel() == D && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "qk norm: gamma f32 [D]");
+  *q_gamma = qg->data_ptr<float>();
+  *k_gamma = kg->data_ptr<float>();
+  return true;
+}
+
 // qkv [T, >= (H + 2 Hkv) D] bf16 (rotated in place); pos int32 [T]; cos_sin f32 [P, D/2, 2];
-// slots int64 [T] (optional): writes rotated k / v into the paged cache.
+// slots int64 [T] (optional): writes rotated k / v into the paged cache.  q_gamma / k_gamma f32 [D]
+// (optional): per-head RMSNorm of q and k before the rotation.
 void rope_kv(at::Tensor qkv, const at::Tensor& pos, const at::Tensor& cos_sin, const c10::optional<at::Tensor>& slots,
-             at::Tensor k_cache, at::Tensor v_cache, int64_t H, int64_t Hkv, int64_t D) {
+             at::Tensor k_cache, at::Tensor v_cache, int64_t H, int64_t Hkv, int64_t D,
+             const c10::optional<at::Tensor>& q_gamma, const c10::optional<at::Tensor>& k_gamma, double qk_eps) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1, "qkv");
   TORCH_CHECK(qkv.size(1) >= (H + 2 * Hkv) * D, "qkv: too few columns");
   TORCH_CHECK(D % 2 == 0 && D <= 256, "rope: head dim");
@@ -61,6 +79,7 @@ void rope_kv(at::Tensor qkv, const at::Tensor& pos, const at::Tensor& cos_sin, c
     a.k_cache = reinterpret_cast<uint16_t*>(k_cache.data_ptr()); a.v_cache = reinterpret_cast<uint16_t*>(v_cache.data_ptr());
   }
   a.T = (int)T; a.H = (int)H; a.Hkv = (int)Hkv; a.D = (int)D;
+  if (check_qk_norm(q_gamma, k_gamma, qk_eps, D, qkv, &a.q_gamma, &a.k_gamma)) a.eps = (float)qk_eps;
   const at::DeviceGuard g(qkv.device());
   CHECK_HIP3(lumen::rope_kv(a, cur()));
 }
@@ -445,7 +464,7 @@ void upload_small(const at::Tensor& src, at::Tensor out) {
 TORCH_LIBRARY_FRAGMENT(lumen, m) {
   m.def("upload_small(Tensor src, Tensor(o!) out) -> ()");
   m.def("rope_kv(Tensor(a!) qkv, Tensor pos, Tensor cos_sin, Tensor? slots, Tensor(k!) k_cache, Tensor(v!) v_cache, "
-        "int H, int Hkv, int D) -> ()");
+        "int H, int Hkv, int D, Tensor? q_gamma=None, Tensor? k_gamma=None, float qk_eps=0.0) -> ()");
   m.def("paged_decode(Tensor q, Tensor(k!) k_cache, Tensor(v!) v_cache, Tensor block_table, Tensor ctx_len, "
         "Tensor(o!) out, int H, int Hkv, float scale, int nsplit, int blocks_per_split, Tensor(p!)? part_o=None, "
         "Tensor(m!)? part_ml=None, Tensor? pos=None, Tensor? cos_sin=None, Tensor? slots=None, Tensor? pf0=None, "

@@ -1,10 +1,12 @@
-"""Llama / Qwen2 decoder for the VLM, tensor-parallel over RCCL.
+"""Llama / Qwen2 / Qwen3 decoder for the VLM, tensor-parallel over RCCL.
 
 Reference: the FastVLM decoder ONNX graph (Qwen2-0.5B) driven by
 packages/lumen-vlm/src/lumen_vlm/backends/onnxrt_backend.py:161-533; the north star
 adds Llama-3-8B (LLaVA-style) at TP=8.  Per layer (every op one gfx950 kernel):
 
   RMSNorm (fused residual add)  ->  QKV GEMM (+bias, Qwen2)  ->  RoPE + paged-KV write
+  (Qwen3: q and k heads first pass through an RMSNorm over head_dim, inside the same kernel;
+  its decode steps keep this launch, since the attention kernel's fused RoPE has no norm)
   ->  attention (prefill: flash kernel reading the rotated QKV in place, causal;
       decode: paged flash-decoding)  ->  o_proj GEMM  ->  RMSNorm  ->  gate|up GEMM with
   the SwiGLU epilogue  ->  down GEMM
@@ -14,7 +16,8 @@ whole 8-column GLU groups per rank), o_proj and down are row-parallel followed b
 an all-reduce (RCCL); with TP the residual add is fused into the next RMSNorm
 (``norm(add=partial, resid_out=x)``) instead of the GEMM epilogue.  Embedding and
 lm_head are vocab-parallel (masked lookup + all-reduce; local top-k + all-gather of
-the candidates for sampling).  Weights can be loaded from HF Qwen2/Llama state dicts
+the candidates for sampling).  The Qwen3 q / k norm weights ([head_dim], shared by all heads)
+are replicated on every rank.  Weights can be loaded from HF Qwen2/Qwen3/Llama state dicts
 (sharded at load) or random-initialised per rank directly on the device.
 """
 from __future__ import annotations
@@ -75,6 +78,7 @@ class LLMConfig:
     max_position: int = 32768
     tie_word_embeddings: bool = True
     qkv_bias: bool = True
+    qk_norm: bool = False            # Qwen3: RMSNorm over head_dim on every q / k head before RoPE
     rope_scaling: Optional[dict] = None
     bos_token_id: int = 151643
     eos_token_id: int = 151645
@@ -94,7 +98,8 @@ class LLMConfig:
                          intermediate_size=c["intermediate_size"], rope_theta=c.get("rope_theta", 10000.0),
                          rms_eps=c.get("rms_norm_eps", 1e-6), max_position=c.get("max_position_embeddings", 4096),
                          tie_word_embeddings=c.get("tie_word_embeddings", False),
-                         qkv_bias=c.get("attention_bias", mt == "qwen2"), rope_scaling=c.get("rope_scaling"),
+                         qkv_bias=c.get("attention_bias", mt == "qwen2"), qk_norm=mt == "qwen3",
+                         rope_scaling=c.get("rope_scaling"),
                          bos_token_id=c.get("bos_token_id") or 0,
                          eos_token_id=(c.get("eos_token_id")[0] if isinstance(c.get("eos_token_id"), list)
                                        else c.get("eos_token_id") or 0))
@@ -113,8 +118,18 @@ LLM_PRESETS = {
                            head_dim=128, intermediate_size=11008, rope_theta=10000.0, rms_eps=1e-5,
                            max_position=4096, tie_word_embeddings=False, qkv_bias=False, bos_token_id=1,
                            eos_token_id=2),
+    "qwen3-0.6b": LLMConfig(vocab_size=151936, hidden_size=1024, num_layers=28, num_heads=16, num_kv_heads=8,
+                            head_dim=128, intermediate_size=3072, rope_theta=1000000.0, rms_eps=1e-6,
+                            max_position=40960, tie_word_embeddings=True, qkv_bias=False, qk_norm=True),
+    "qwen3-8b": LLMConfig(vocab_size=151936, hidden_size=4096, num_layers=36, num_heads=32, num_kv_heads=8,
+                          head_dim=128, intermediate_size=12288, rope_theta=1000000.0, rms_eps=1e-6,
+                          max_position=40960, tie_word_embeddings=False, qkv_bias=False, qk_norm=True),
     "tiny": LLMConfig(vocab_size=512, hidden_size=128, num_layers=2, num_heads=4, num_kv_heads=2, head_dim=32,
                       intermediate_size=256, max_position=2048, bos_token_id=1, eos_token_id=2),
+    # Qwen3 test shape: q / k norms, head_dim 64 (the RoPE tile kernel's smallest) and heads x head_dim != hidden
+    "tiny-qwen3": LLMConfig(vocab_size=512, hidden_size=128, num_layers=2, num_heads=4, num_kv_heads=2, head_dim=64,
+                            intermediate_size=256, max_position=2048, qkv_bias=False, qk_norm=True, bos_token_id=1,
+                            eos_token_id=2),
     # TP = 4 / 8 test shapes: 8 query heads over 8 KV heads (one of each per rank at TP = 8) and over
     # 2 KV heads (GQA: every KV head replicated on TP / 2 ranks, the kv_rep > 1 load path)
     "tiny-h8": LLMConfig(vocab_size=512, hidden_size=256, num_layers=2, num_heads=8, num_kv_heads=8, head_dim=32,
@@ -148,6 +163,11 @@ class DecoderLayer(nn.Module):
         self.qkv_w = nn.Parameter(torch.zeros((self.H + 2 * self.Hkv) * D, Hd, **kw), requires_grad=False)
         self.qkv_b = nn.Parameter(torch.zeros((self.H + 2 * self.Hkv) * D, dtype=torch.float32, device=device),
                                   requires_grad=False) if cfg.qkv_bias else None
+        # Qwen3: RMSNorm weights over head_dim, shared by all q (k) heads, hence replicated under TP
+        self.q_norm = nn.Parameter(torch.ones(D, dtype=torch.float32, device=device),
+                                   requires_grad=False) if cfg.qk_norm else None
+        self.k_norm = nn.Parameter(torch.ones(D, dtype=torch.float32, device=device),
+                                   requires_grad=False) if cfg.qk_norm else None
         self.o_w = nn.Parameter(torch.zeros(Hd, self.H * D, **kw), requires_grad=False)
         self.gu_w = nn.Parameter(torch.zeros(2 * self.I, Hd, **kw), requires_grad=False)
         self.down_w = nn.Parameter(torch.zeros(Hd, self.I, **kw), requires_grad=False)
@@ -200,10 +220,19 @@ class LLM(nn.Module):
             rnd(l.down_w, (l.I * self.tp.world) ** -0.5 / math.sqrt(2 * L))
             if l.qkv_b is not None:
                 rnd(l.qkv_b, 0.02)
+        if self.cfg.qk_norm:
+            # replicated under TP: one generator for every rank; drawn around 1 so that no test
+            # passes with the gammas ignored
+            gn = torch.Generator(device=dev).manual_seed(seed * 1000 + 999)
+            for l in self.layers:
+                for p in (l.q_norm, l.k_norm):
+                    p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=gn, device=dev, dtype=torch.float32))
 
     @torch.no_grad()
     def load_hf_state_dict(self, sd: dict, prefix: str = "model.") -> None:
-        """HF Qwen2 / Llama weights (``model.layers.N.self_attn.q_proj.weight`` ...), sharded for this rank."""
+        """HF Qwen2 / Qwen3 / Llama weights (``model.layers.N.self_attn.q_proj.weight`` ...), sharded for
+        this rank.  The Qwen3 ``self_attn.{q,k}_norm.weight`` must be present exactly when
+        ``cfg.qk_norm`` is set: a decoder that dropped them would serve wrong tokens silently."""
         cfg, r, w = self.cfg, self.tp.rank, self.tp.world
         D = cfg.head_dim
 
@@ -233,6 +262,15 @@ class LLM(nn.Module):
                 bk = rows(get(p + "self_attn.k_proj.bias"), kvn, kvi)
                 bv = rows(get(p + "self_attn.v_proj.bias"), kvn, kvi)
                 l.qkv_b.copy_(torch.cat([bq, bk, bv], 0))
+            for name, dst in (("q_norm", l.q_norm), ("k_norm", l.k_norm)):
+                key = f"{p}self_attn.{name}.weight"
+                if dst is not None:
+                    if key not in sd:
+                        raise KeyError(f"{key}: missing from the state dict of a qk_norm (Qwen3) decoder")
+                    dst.copy_(get(key))
+                elif key in sd:
+                    raise ValueError(f"{key}: the state dict has q / k norm weights but the config has "
+                                     "qk_norm=False (a Qwen3 checkpoint needs model_type 'qwen3')")
             o = get(p + "self_attn.o_proj.weight")
             l.o_w.copy_(o[:, r * l.H * D:(r + 1) * l.H * D].to(l.o_w.dtype))
             gate = rows(get(p + "mlp.gate_proj.weight"), w, r)
@@ -418,12 +456,19 @@ class LLM(nn.Module):
         e = e.view(-1, self.cfg.hidden_size)
         return self._all_reduce(e)
 
+    def _qk_norm(self, l) -> Optional[tuple]:
+        """(q_gamma, k_gamma, eps) of a layer for the RoPE kernels (None: no q / k norm)."""
+        return (l.q_norm, l.k_norm, self.cfg.rms_eps) if l.q_norm is not None else None
+
+    def _rope_kv(self, qkv, pos, l, slots, kc, vc) -> None:
+        """(q / k norm +) RoPE in place on the packed QKV rows + the paged KV-cache write of one layer."""
+        lops.rope_kv(qkv, pos, self.cos_sin, l.H, l.Hkv, self.cfg.head_dim, slots, kc, vc, qk_norm=self._qk_norm(l))
+
     def _layers(self, x: torch.Tensor, pos: torch.Tensor, slots: Optional[torch.Tensor], kv, attn_fn) -> torch.Tensor:
         """x [T, hidden] residual stream (updated in place); returns x."""
         if self._f8_ok(x.shape[0]):
             return self._layers_f8(x, pos, slots, kv, attn_fn)
         cfg = self.cfg
-        D = cfg.head_dim
         eps = cfg.rms_eps
         T = x.shape[0]
         h = torch.empty_like(x)
@@ -444,7 +489,7 @@ class LLM(nn.Module):
             qkv = self._lin(h, l, "qkv", bias=l.qkv_b)
             kc, vc = (kv.k[i], kv.v[i]) if kv is not None else (None, None)
             if not getattr(attn_fn, "fuses_rope", False):
-                lops.rope_kv(qkv, pos, self.cos_sin, l.H, l.Hkv, D, slots, kc, vc)
+                self._rope_kv(qkv, pos, l, slots, kc, vc)
             att = attn_fn(qkv, l, kc, vc)                            # [T, H*D]
             if tp:
                 part = self._lin(att, l, "o")
@@ -466,7 +511,7 @@ class LLM(nn.Module):
         """Decode layer stack (<= 32 rows, norms folded): 4 GEMM launches per layer and no norm
         kernel -- o / down write the residual stream plus its per-tile sums of squares
         (``ssq``), qkv / gate|up scale their rows by the rstd those give (ops.linear_dec)."""
-        D, eps = self.cfg.head_dim, self.cfg.rms_eps
+        eps = self.cfg.rms_eps
         ssq = self._ssq_buf(x.device)
         for i, l in enumerate(self.layers):
             # layer 0 reads the embeddings (no producer GEMM): rstd from x itself
@@ -474,7 +519,7 @@ class LLM(nn.Module):
                                  ssq_in=ssq if i > 0 else None)
             kc, vc = (kv.k[i], kv.v[i]) if kv is not None else (None, None)
             if not getattr(attn_fn, "fuses_rope", False):      # decode attention rotates + caches itself
-                lops.rope_kv(qkv, pos, self.cos_sin, l.H, l.Hkv, D, slots, kc, vc)
+                self._rope_kv(qkv, pos, l, slots, kc, vc)
             att = attn_fn(qkv, l, kc, vc)
             ops.linear_dec(att, l.o_w, getattr(l, "o_s", None), residual=x, out=x, ssq_out=ssq)
             g = ops.linear_dec(x, l.gu_w, getattr(l, "gu_s", None), glu=True, norm_eps=eps, ssq_in=ssq)
@@ -487,7 +532,7 @@ class LLM(nn.Module):
         produces it (RMSNorm+quant for qkv / gate|up, a row-quant pass for o / down) and the
         GEMMs run fp8 x fp8 (csrc/gemm_f8.hip).  Same TP structure as :meth:`_layers`."""
         cfg = self.cfg
-        D, eps, T = cfg.head_dim, cfg.rms_eps, x.shape[0]
+        eps, T = cfg.rms_eps, x.shape[0]
         dev = x.device
         h8 = torch.empty((T, x.shape[1]), device=dev, dtype=torch.float8_e4m3fn)
         hs = torch.empty((T,), device=dev, dtype=torch.float32)
@@ -500,7 +545,7 @@ class LLM(nn.Module):
             ops.rms_norm_quant_fp8(x, l.ln1, eps, add=add, resid_out=x if add is not None else None, out=h8, scale=hs)
             qkv = self._lin8(h8, hs, l, "qkv", bias=l.qkv_b)
             kc, vc = (kv.k[i], kv.v[i]) if kv is not None else (None, None)
-            lops.rope_kv(qkv, pos, self.cos_sin, l.H, l.Hkv, D, slots, kc, vc)
+            self._rope_kv(qkv, pos, l, slots, kc, vc)
             att = attn_fn(qkv, l, kc, vc)                            # [T, H*D] bf16
             a8, as_ = ops.quant_rows_fp8(att)
             if tp:
@@ -573,7 +618,7 @@ class LLM(nn.Module):
                 lin(c, l, "qkv", h8 if f8 else h, hs if f8 else None, bias=l.qkv_b, out=qkv[a:b])
             kc, vc = (kv.k[i], kv.v[i]) if kv is not None else (None, None)
             if not getattr(attn_fn, "fuses_rope", False):
-                lops.rope_kv(qkv, pos, self.cos_sin, l.H, l.Hkv, D, slots, kc, vc)
+                self._rope_kv(qkv, pos, l, slots, kc, vc)
             att = attn_fn(qkv, l, kc, vc)                            # [T, H*D]
             if f8:
                 a8, as_ = ops.quant_rows_fp8(att)
@@ -653,8 +698,11 @@ class LLM(nn.Module):
         x = self.embed_tokens(ids)
         self._maybe_fold(x)
 
+        # (a q / k norm sits before the rotation, which the attention kernel's fused form does not
+        # have: Qwen3 decode keeps the rope_kv launch, whose kernels apply the norm)
         fuse = _FUSED_DECODE_ROPE and x.is_cuda and self.cfg.head_dim in (64, 128) and \
-            self.norm_folded and x.shape[0] <= 32 and not self.tp.enabled and kv is not None
+            self.norm_folded and x.shape[0] <= 32 and not self.tp.enabled and kv is not None and \
+            not self.cfg.qk_norm
 
         def attn(qkv, l, kc, vc):
             return lops.paged_decode(qkv, kc, vc, block_table, ctx_len, l.H, l.Hkv, workspace=workspace,

@@ -47,23 +47,49 @@ def _rot_ref(x: torch.Tensor, cs: torch.Tensor) -> torch.Tensor:
     return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1)
 
 
+def _qk_norm_ref(x: torch.Tensor, H: int, qk_norm: tuple) -> torch.Tensor:
+    """x [T, H + Hkv, D] fp32 -> per-head RMSNorm over D: q heads with q_gamma, k heads with k_gamma."""
+    q_gamma, k_gamma, eps = qk_norm
+    rstd = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + float(eps))
+    gamma = torch.cat([q_gamma.float().expand(H, -1), k_gamma.float().expand(x.shape[1] - H, -1)], 0)
+    return x * rstd * gamma[None]
+
+
+def _qk_norm_args(op, qk_norm: Optional[tuple]) -> tuple:
+    """Trailing (q_gamma, k_gamma, eps) arguments of a HIP op; a library built without them is an error."""
+    if qk_norm is None:
+        return ()
+    if not any(a.name == "q_gamma" for a in op.default._schema.arguments):
+        raise RuntimeError(f"{op.default._schema.name}: the native HIP library was built without the per-head "
+                           "q / k RMSNorm arguments; rebuild it (python -m lumen_amd._build)")
+    q_gamma, k_gamma, eps = qk_norm
+    return q_gamma, k_gamma, float(eps)
+
+
 def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, cos_sin: torch.Tensor, H: int, Hkv: int, D: int,
             slots: Optional[torch.Tensor] = None, k_cache: Optional[torch.Tensor] = None,
-            v_cache: Optional[torch.Tensor] = None) -> None:
+            v_cache: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> None:
     """Rotate q and k heads of qkv [T, (H + 2Hkv) D] in place; with ``slots`` also write k / v
-    of every token into the paged cache (slot = block * 64 + offset, < 0 skipped)."""
+    of every token into the paged cache (slot = block * 64 + offset, < 0 skipped).
+
+    ``qk_norm = (q_gamma [D], k_gamma [D], eps)`` (fp32, Qwen3): every q / k head vector passes
+    through an RMSNorm over D before the rotation, in fp32, rounded once after the rotation;
+    v is untouched.  Head dims 32 / 64 / 128 on the GPU."""
     T = qkv.shape[0]
     if qkv.is_cuda:
-        hip_ops().rope_kv(qkv, pos.to(torch.int32).contiguous(), cos_sin,
-                          slots.to(torch.long).contiguous() if slots is not None else None,
-                          k_cache if k_cache is not None else qkv, v_cache if v_cache is not None else qkv,
-                          int(H), int(Hkv), int(D))
+        op = hip_ops().rope_kv
+        op(qkv, pos.to(torch.int32).contiguous(), cos_sin,
+           slots.to(torch.long).contiguous() if slots is not None else None,
+           k_cache if k_cache is not None else qkv, v_cache if v_cache is not None else qkv,
+           int(H), int(Hkv), int(D), *_qk_norm_args(op, qk_norm))
         return
     if T == 0:
         return
     cs = cos_sin[pos.long()]
     nq = (H + Hkv) * D
     x = qkv[:, :nq].float().view(T, H + Hkv, D)
+    if qk_norm is not None:
+        x = _qk_norm_ref(x, H, qk_norm)
     xr = _rot_ref(x, cs).to(qkv.dtype)
     qkv[:, :nq] = xr.view(T, nq)
     if slots is not None:
