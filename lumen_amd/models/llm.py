@@ -1,4 +1,4 @@
-"""Llama / Qwen2 / Qwen3 decoder for the VLM, tensor-parallel over RCCL.
+"""Llama / Qwen2 / Qwen3 / Qwen3-MoE decoder for the VLM, tensor-parallel over RCCL.
 
 Reference: the FastVLM decoder ONNX graph (Qwen2-0.5B) driven by
 packages/lumen-vlm/src/lumen_vlm/backends/onnxrt_backend.py:161-533; the north star
@@ -10,6 +10,16 @@ adds Llama-3-8B (LLaVA-style) at TP=8.  Per layer (every op one gfx950 kernel):
   ->  attention (prefill: flash kernel reading the rotated QKV in place, causal;
       decode: paged flash-decoding)  ->  o_proj GEMM  ->  RMSNorm  ->  gate|up GEMM with
   the SwiGLU epilogue  ->  down GEMM
+
+Qwen3-MoE (``num_experts > 0``): the MLP of every layer is sparse -- RMSNorm -> router (fp32
+logits, top-k, ties to the lower id) -> the chosen experts' gate|up + SwiGLU and down GEMMs over
+rows grouped by expert on the device -> weighted combine into the residual stream
+(``ops.llm.moe_mlp``, csrc/moe.hip).  No host read and launches sized from the shapes alone, so
+decode and verify steps are captured into graphs like the dense ones.  Such a decoder runs the
+unfolded layer stack at every row count; out of scope and refused with an error: quantised experts
+(``quantize_fp8`` / ``quantize_w4``), tensor / expert parallelism (``tp.world > 1``), the
+norm-folded decode chain (``fold_norms`` leaves it unfolded) and mixed dense / sparse stacks
+(``decoder_sparse_step != 1``, ``mlp_only_layers``).
 
 Tensor parallelism (Megatron): QKV and gate|up are column-parallel (whole heads /
 whole 8-column GLU groups per rank), o_proj and down are row-parallel followed by
@@ -82,6 +92,12 @@ class LLMConfig:
     rope_scaling: Optional[dict] = None
     bos_token_id: int = 151643
     eos_token_id: int = 151645
+    # Qwen3-MoE: every layer's MLP is num_experts small SwiGLU experts of which a router picks
+    # num_experts_per_tok per token (0 experts: the dense MLP of intermediate_size)
+    num_experts: int = 0
+    num_experts_per_tok: int = 0
+    moe_intermediate_size: int = 0
+    norm_topk_prob: bool = True
 
     @staticmethod
     def from_dict(d: dict) -> "LLMConfig":
@@ -93,16 +109,27 @@ class LLMConfig:
         H = c["num_attention_heads"]
         hd = c.get("head_dim") or c["hidden_size"] // H
         mt = c.get("model_type", "llama")
+        moe = {}
+        if mt == "qwen3_moe":
+            if c.get("decoder_sparse_step", 1) != 1:
+                raise ValueError(f"qwen3_moe: decoder_sparse_step = {c.get('decoder_sparse_step')}; only stacks whose "
+                                 "every layer is sparse (decoder_sparse_step 1) are supported")
+            if c.get("mlp_only_layers"):
+                raise ValueError(f"qwen3_moe: mlp_only_layers = {c.get('mlp_only_layers')}; mixed dense / sparse "
+                                 "stacks are not supported")
+            moe = dict(num_experts=c["num_experts"], num_experts_per_tok=c["num_experts_per_tok"],
+                       moe_intermediate_size=c["moe_intermediate_size"],
+                       norm_topk_prob=bool(c.get("norm_topk_prob", False)))
         return LLMConfig(vocab_size=c["vocab_size"], hidden_size=c["hidden_size"], num_layers=c["num_hidden_layers"],
                          num_heads=H, num_kv_heads=c.get("num_key_value_heads", H), head_dim=hd,
                          intermediate_size=c["intermediate_size"], rope_theta=c.get("rope_theta", 10000.0),
                          rms_eps=c.get("rms_norm_eps", 1e-6), max_position=c.get("max_position_embeddings", 4096),
                          tie_word_embeddings=c.get("tie_word_embeddings", False),
-                         qkv_bias=c.get("attention_bias", mt == "qwen2"), qk_norm=mt == "qwen3",
+                         qkv_bias=c.get("attention_bias", mt == "qwen2"), qk_norm=mt in ("qwen3", "qwen3_moe"),
                          rope_scaling=c.get("rope_scaling"),
                          bos_token_id=c.get("bos_token_id") or 0,
                          eos_token_id=(c.get("eos_token_id")[0] if isinstance(c.get("eos_token_id"), list)
-                                       else c.get("eos_token_id") or 0))
+                                       else c.get("eos_token_id") or 0), **moe)
 
     def to_dict(self):
         return asdict(self)
@@ -124,12 +151,23 @@ LLM_PRESETS = {
     "qwen3-8b": LLMConfig(vocab_size=151936, hidden_size=4096, num_layers=36, num_heads=32, num_kv_heads=8,
                           head_dim=128, intermediate_size=12288, rope_theta=1000000.0, rms_eps=1e-6,
                           max_position=40960, tie_word_embeddings=False, qkv_bias=False, qk_norm=True),
+    # Qwen3-30B-A3B: 128 experts of 768, 8 per token (~3 B active parameters per decode step)
+    "qwen3-30b-a3b": LLMConfig(vocab_size=151936, hidden_size=2048, num_layers=48, num_heads=32, num_kv_heads=4,
+                               head_dim=128, intermediate_size=6144, rope_theta=1000000.0, rms_eps=1e-6,
+                               max_position=40960, tie_word_embeddings=False, qkv_bias=False, qk_norm=True,
+                               num_experts=128, num_experts_per_tok=8, moe_intermediate_size=768,
+                               norm_topk_prob=True),
     "tiny": LLMConfig(vocab_size=512, hidden_size=128, num_layers=2, num_heads=4, num_kv_heads=2, head_dim=32,
                       intermediate_size=256, max_position=2048, bos_token_id=1, eos_token_id=2),
     # Qwen3 test shape: q / k norms, head_dim 64 (the RoPE tile kernel's smallest) and heads x head_dim != hidden
     "tiny-qwen3": LLMConfig(vocab_size=512, hidden_size=128, num_layers=2, num_heads=4, num_kv_heads=2, head_dim=64,
                             intermediate_size=256, max_position=2048, qkv_bias=False, qk_norm=True, bos_token_id=1,
                             eos_token_id=2),
+    # Qwen3-MoE test shape: tiny-qwen3 with 8 experts of 64, 2 per token
+    "tiny-qwen3-moe": LLMConfig(vocab_size=512, hidden_size=128, num_layers=2, num_heads=4, num_kv_heads=2,
+                                head_dim=64, intermediate_size=256, max_position=2048, qkv_bias=False, qk_norm=True,
+                                bos_token_id=1, eos_token_id=2, num_experts=8, num_experts_per_tok=2,
+                                moe_intermediate_size=64, norm_topk_prob=True),
     # TP = 4 / 8 test shapes: 8 query heads over 8 KV heads (one of each per rank at TP = 8) and over
     # 2 KV heads (GQA: every KV head replicated on TP / 2 ranks, the kv_rep > 1 load path)
     "tiny-h8": LLMConfig(vocab_size=512, hidden_size=256, num_layers=2, num_heads=8, num_kv_heads=8, head_dim=32,
@@ -169,8 +207,17 @@ class DecoderLayer(nn.Module):
         self.k_norm = nn.Parameter(torch.ones(D, dtype=torch.float32, device=device),
                                    requires_grad=False) if cfg.qk_norm else None
         self.o_w = nn.Parameter(torch.zeros(Hd, self.H * D, **kw), requires_grad=False)
-        self.gu_w = nn.Parameter(torch.zeros(2 * self.I, Hd, **kw), requires_grad=False)
-        self.down_w = nn.Parameter(torch.zeros(Hd, self.I, **kw), requires_grad=False)
+        self.E = cfg.num_experts
+        if self.E > 0:
+            # sparse MLP (ops.llm.moe_mlp): router [E, hidden], per expert gate|up interleaved as
+            # ops.glu_interleave [E, 2I, hidden] and down [E, hidden, I], I = moe_intermediate_size
+            self.I = cfg.moe_intermediate_size
+            self.router_w = nn.Parameter(torch.zeros(self.E, Hd, **kw), requires_grad=False)
+            self.gu_w = nn.Parameter(torch.zeros(self.E, 2 * self.I, Hd, **kw), requires_grad=False)
+            self.down_w = nn.Parameter(torch.zeros(self.E, Hd, self.I, **kw), requires_grad=False)
+        else:
+            self.gu_w = nn.Parameter(torch.zeros(2 * self.I, Hd, **kw), requires_grad=False)
+            self.down_w = nn.Parameter(torch.zeros(Hd, self.I, **kw), requires_grad=False)
 
 
 class LLM(nn.Module):
@@ -181,6 +228,16 @@ class LLM(nn.Module):
         w = self.tp.world
         assert cfg.num_heads % w == 0 and (cfg.num_kv_heads % w == 0 or w % cfg.num_kv_heads == 0), "TP heads"
         assert cfg.intermediate_size % (8 * w) == 0 and cfg.vocab_size % w == 0, "TP shapes"
+        self.moe = cfg.num_experts > 0
+        if self.moe:
+            if w > 1:
+                raise NotImplementedError("a mixture-of-experts decoder (num_experts > 0) runs on one GPU: tensor / "
+                                          "expert parallelism is not implemented")
+            if not (1 <= cfg.num_experts_per_tok <= min(cfg.num_experts, 8) and cfg.num_experts <= 256):
+                raise ValueError(f"MoE: num_experts <= 256 and 1 <= num_experts_per_tok <= min(num_experts, 8), got "
+                                 f"{cfg.num_experts} / {cfg.num_experts_per_tok}")
+            if cfg.hidden_size % 32 or cfg.moe_intermediate_size % 32 or cfg.moe_intermediate_size <= 0:
+                raise ValueError("MoE: hidden_size and moe_intermediate_size must be multiples of 32")
         self.Vl = cfg.vocab_size // w
         self.v0 = self.tp.rank * self.Vl
         kw = dict(dtype=dtype, device=device)
@@ -218,6 +275,9 @@ class LLM(nn.Module):
             rnd(l.o_w, (Hd ** -0.5) / math.sqrt(2 * L))
             rnd(l.gu_w, Hd ** -0.5)
             rnd(l.down_w, (l.I * self.tp.world) ** -0.5 / math.sqrt(2 * L))
+            if self.moe:
+                # unit-scale router logits for unit-RMS rows: distinct experts per token, no one-hot softmax
+                rnd(l.router_w, Hd ** -0.5)
             if l.qkv_b is not None:
                 rnd(l.qkv_b, 0.02)
         if self.cfg.qk_norm:
@@ -273,13 +333,43 @@ class LLM(nn.Module):
                                      "qk_norm=False (a Qwen3 checkpoint needs model_type 'qwen3')")
             o = get(p + "self_attn.o_proj.weight")
             l.o_w.copy_(o[:, r * l.H * D:(r + 1) * l.H * D].to(l.o_w.dtype))
+            l.ln1.copy_(get(p + "input_layernorm.weight").to(l.ln1.dtype))
+            l.ln2.copy_(get(p + "post_attention_layernorm.weight").to(l.ln2.dtype))
+            if self.moe:
+                self._load_experts(sd, p, l)
+                continue
+            for key in (p + "mlp.gate.weight", p + "mlp.experts.0.gate_proj.weight"):
+                if key in sd:
+                    raise ValueError(f"{key}: the state dict holds a mixture-of-experts MLP but the config is dense "
+                                     "(num_experts = 0; a Qwen3-MoE checkpoint needs model_type 'qwen3_moe')")
+            if p + "mlp.gate_proj.weight" not in sd:
+                raise KeyError(f"{p}mlp.gate_proj.weight: missing from the state dict of a dense decoder")
             gate = rows(get(p + "mlp.gate_proj.weight"), w, r)
             up = rows(get(p + "mlp.up_proj.weight"), w, r)
             l.gu_w.copy_(ops.glu_interleave(gate, up).to(l.gu_w.dtype))
             dn = get(p + "mlp.down_proj.weight")
             l.down_w.copy_(dn[:, r * l.I:(r + 1) * l.I].to(l.down_w.dtype))
-            l.ln1.copy_(get(p + "input_layernorm.weight").to(l.ln1.dtype))
-            l.ln2.copy_(get(p + "post_attention_layernorm.weight").to(l.ln2.dtype))
+
+    def _load_experts(self, sd: dict, p: str, l) -> None:
+        """The sparse MLP of layer prefix ``p``: ``mlp.gate.weight`` (router) and
+        ``mlp.experts.{e}.{gate,up,down}_proj.weight``, gate and up interleaved per expert."""
+        if p + "mlp.gate_proj.weight" in sd:
+            raise ValueError(f"{p}mlp.gate_proj.weight: the state dict holds a dense MLP but the config has "
+                             f"num_experts = {l.E}")
+        keys = [p + "mlp.gate.weight"] + [f"{p}mlp.experts.{e}.{n}_proj.weight" for e in range(l.E)
+                                           for n in ("gate", "up", "down")]
+        for key in keys:
+            if key not in sd:
+                raise KeyError(f"{key}: missing from the state dict of a mixture-of-experts decoder "
+                               f"(num_experts = {l.E})")
+        if f"{p}mlp.experts.{l.E}.gate_proj.weight" in sd:
+            raise ValueError(f"{p}mlp.experts.{l.E}.gate_proj.weight: the state dict has more experts than the "
+                             f"config (num_experts = {l.E})")
+        l.router_w.copy_(sd[keys[0]].to(torch.float32).to(l.router_w.dtype))
+        for e in range(l.E):
+            gate, up, dn = (sd[f"{p}mlp.experts.{e}.{n}_proj.weight"].to(torch.float32) for n in ("gate", "up", "down"))
+            l.gu_w[e].copy_(ops.glu_interleave(gate, up).to(l.gu_w.dtype))
+            l.down_w[e].copy_(dn.to(l.down_w.dtype))
 
     @torch.no_grad()
     def fold_norms(self) -> None:
@@ -290,7 +380,7 @@ class LLM(nn.Module):
         no normalised copy of x per token.  fp8 weights are dequantised, folded and
         requantised per row, 4-bit weights per group (same group size).  Weight loads reset
         the flag."""
-        if self.norm_folded:
+        if self.norm_folded or self.moe:     # a MoE decoder keeps its norm kernels (the router reads the normalised rows)
             return
 
         def fold(obj, wname, gamma):
@@ -330,7 +420,7 @@ class LLM(nn.Module):
     def _maybe_fold(self, x: torch.Tensor) -> None:
         # never inside a graph capture: the in-place weight rewrite would be replayed every step
         # (the engine warms up eagerly before capturing, so the fold has happened by then)
-        if x.is_cuda and _FUSED_DECODE_NORM and not self.norm_folded and \
+        if x.is_cuda and _FUSED_DECODE_NORM and not self.norm_folded and not self.moe and \
                 not torch.cuda.is_current_stream_capturing():
             self.fold_norms()
             self._ssq_buf(x.device)
@@ -342,6 +432,8 @@ class LLM(nn.Module):
         are HBM-bound on weights and stream the fp8 weights into bf16 MFMAs (half the bytes
         per token); prefill quantises the activations per token and runs fp8 x fp8 on the
         block-scaled matrix cores (:meth:`_f8_ok`).  Accumulation and epilogues are fp32."""
+        if self.moe:
+            raise NotImplementedError("quantize_fp8: quantised experts are not implemented for a mixture-of-experts decoder")
         if self.weight_dtype == "fp8":
             return
         for l in self.layers:
@@ -364,6 +456,8 @@ class LLM(nn.Module):
         count (csrc/gemm_w4.hip); the embedding stays bf16.  The RMSNorm gammas are folded
         first (on any device) and ``norm_folded`` stays set, so the codes are never
         requantised by a later fold."""
+        if self.moe:
+            raise NotImplementedError("quantize_w4: quantised experts are not implemented for a mixture-of-experts decoder")
         if self.weight_dtype == "w4":
             return
         assert self.weight_dtype == "bf16", "quantize_w4 starts from float weights"
@@ -497,6 +591,11 @@ class LLM(nn.Module):
             else:
                 self._lin(att, l, "o", residual=x, out=x)
                 ops.rms_norm(x, l.ln2, eps, out=h)
+            if self.moe:     # sparse MLP at every row count (no TP): route, grouped expert GEMMs, combine into x
+                lops.moe_mlp(h, l.router_w, l.gu_w, l.down_w, cfg.num_experts_per_tok, norm_topk=cfg.norm_topk_prob,
+                             residual=x, out=x)
+                del qkv, att
+                continue
             g = self._lin(h, l, "gu", glu=True)
             if tp:
                 pending = self._lin(g, l, "down")

@@ -146,6 +146,9 @@ VLM_PRESETS = {
                            llm=LLM_PRESETS["tiny-gqa8"], image_token_id=259),
     "tiny-qwen3": VLMConfig(vision=VisionConfig(image_size=32, patch_size=8, width=64, layers=2, heads=2, act="gelu"),
                             llm=LLM_PRESETS["tiny-qwen3"], image_token_id=259),
+    "tiny-qwen3-moe": VLMConfig(vision=VisionConfig(image_size=32, patch_size=8, width=64, layers=2, heads=2,
+                                                    act="gelu"),
+                                llm=LLM_PRESETS["tiny-qwen3-moe"], image_token_id=259),
     "tiny-fastvit": VLMConfig(vision=VisionConfig(image_size=64, patch_size=16, width=128, layers=0, heads=1),
                               vision_arch="fastvit", fastvit=FASTVIT_PRESETS["tiny-ln"], llm=LLM_PRESETS["tiny"],
                               image_token_id=259),
@@ -468,10 +471,18 @@ class VLM(nn.Module):
             if ly.q_norm is not None:
                 sd[p + "self_attn.q_norm.weight"], sd[p + "self_attn.k_norm.weight"] = ly.q_norm, ly.k_norm
             sd[p + "self_attn.o_proj.weight"] = ly.o_w
-            gu = ly.gu_w.view(ly.I // 8, 2, 8, -1)
-            sd[p + "mlp.gate_proj.weight"] = gu[:, 0].reshape(ly.I, -1)
-            sd[p + "mlp.up_proj.weight"] = gu[:, 1].reshape(ly.I, -1)
-            sd[p + "mlp.down_proj.weight"] = ly.down_w
+            if ly.E > 0:     # Qwen3-MoE names: the router and every expert's projections
+                sd[p + "mlp.gate.weight"] = ly.router_w
+                for e in range(ly.E):
+                    gu = ly.gu_w[e].view(ly.I // 8, 2, 8, -1)
+                    sd[f"{p}mlp.experts.{e}.gate_proj.weight"] = gu[:, 0].reshape(ly.I, -1)
+                    sd[f"{p}mlp.experts.{e}.up_proj.weight"] = gu[:, 1].reshape(ly.I, -1)
+                    sd[f"{p}mlp.experts.{e}.down_proj.weight"] = ly.down_w[e]
+            else:
+                gu = ly.gu_w.view(ly.I // 8, 2, 8, -1)
+                sd[p + "mlp.gate_proj.weight"] = gu[:, 0].reshape(ly.I, -1)
+                sd[p + "mlp.up_proj.weight"] = gu[:, 1].reshape(ly.I, -1)
+                sd[p + "mlp.down_proj.weight"] = ly.down_w
             sd[p + "input_layernorm.weight"] = ly.ln1
             sd[p + "post_attention_layernorm.weight"] = ly.ln2
         return {k: v.detach().contiguous() for k, v in sd.items()}
@@ -525,7 +536,7 @@ def write_vlm_model(root, name: str, preset: Optional[str] = None, seed: int = 0
                                                             "eos_token": "<|im_end|>", "bos_token": None}, indent=2))
     (root / "lumen_vlm_config.json").write_text(json.dumps(cfg.to_dict(), indent=2))
     if weights is None:
-        weights = preset in ("tiny", "tiny-h8", "tiny-gqa8", "tiny-qwen3")
+        weights = preset in ("tiny", "tiny-h8", "tiny-gqa8", "tiny-qwen3", "tiny-qwen3-moe")
     files = ["tokenizer.json", "tokenizer_config.json", "lumen_vlm_config.json"]
     if weights:
         m = VLM(cfg, dtype=torch.float32, device="cpu")
