@@ -668,7 +668,7 @@ static hipError_t launch_f8_split(const uint8_t* A, int64_t lda, const float* sa
   float* slabs = split_workspace((size_t)S * M * N * sizeof(float), stream);
   if (slabs == nullptr) return launch_f8<NS, WN, F8, BN>(A, lda, sa, W, ldw, sw, C, ldc, M, N, K, ep, stream);
   GemmEpi e{};
-  e.alpha = 1.f;
+  e.alpha = ep.alpha;   // on the partials (linear): the reduce pass runs the rest of the epilogue with alpha = 1
   e.out_f32 = 1;
   e.split_koff = (int64_t)(K / S);
   e.split_cstride = (int64_t)M * N;

@@ -174,6 +174,10 @@ void gemm(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tens
   TORCH_CHECK(!glu || (out.scalar_type() == at::kBFloat16 && out_group == 0 && !(residual.has_value() && residual->defined())),
               "gemm: glu epilogue writes bf16 rows without residual / row remap");
   TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat, "gemm: out dtype");
+  // every epilogue stores 16 bytes at a time (8 bf16 / 4 fp32 elements)
+  TORCH_CHECK(out.stride(0) % (out.scalar_type() == at::kFloat ? 4 : 8) == 0 &&
+                  (reinterpret_cast<uintptr_t>(out.data_ptr()) % 16) == 0,
+              "gemm: out rows must be 16-byte aligned");
   const int64_t last = M - 1;
   const int64_t need_rows = out_group > 0 ? (last / out_group) * out_group_stride + out_row_offset + last % out_group + 1 : M;
   TORCH_CHECK(out.size(0) >= need_rows, "gemm: out has ", out.size(0), " rows, needs ", need_rows);
@@ -194,7 +198,6 @@ void gemm(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tens
   ep.out_row_offset = (int)out_row_offset;
   ep.out_f32 = out.scalar_type() == at::kFloat;
   ep.glu = (int)glu;
-  if (glu) TORCH_CHECK(out.stride(0) % 8 == 0, "gemm: glu out rows must be 16-byte aligned");
   if (prelu.has_value() && prelu->defined()) {
     TORCH_CHECK(prelu->scalar_type() == at::kBFloat16 && prelu->numel() >= N && prelu->is_contiguous(), "gemm: prelu");
     ep.prelu = bf(*prelu);
