@@ -28,23 +28,9 @@
 #include "gemm_w4.h"
 #include "gemm_wdec.h"
 #include "gemm_wtile.h"
+#include "wq_widen.h"
 
 namespace lumen {
-
-__device__ __forceinline__ float h2f_lo(uint32_t p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p & 0xffffu)); }
-__device__ __forceinline__ float h2f_hi(uint32_t p) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(p >> 16)); }
-
-// 8 codes (one dword, nibble i = k i) -> 8 bf16 of code * s + mn, in k order
-__device__ __forceinline__ u32x4_t w4x8_to_bf16(const uint32_t w, const float s, const float mn) {
-  const uint32_t lo = w & 0x0f0f0f0fu, hi = (w >> 4) & 0x0f0f0f0fu;   // byte b: k = 2 b | k = 2 b + 1
-  u32x4_t o;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const float e = (float)((lo >> (8 * b)) & 0xffu), d = (float)((hi >> (8 * b)) & 0xffu);
-    o[b] = pack2bf(fmaf(e, s, mn), fmaf(d, s, mn));
-  }
-  return o;
-}
 
 // ============================================================================ decode, M <= 4
 // Every wave streams whole weight rows: one wave instruction reads 1 KiB contiguous of ONE row

@@ -22,6 +22,7 @@
 #include "gemm_epi.h"
 #include "gemm_wdec.h"
 #include "gemm_wtile.h"
+#include "wq_widen.h"
 
 namespace lumen {
 
@@ -34,11 +35,6 @@ template <bool NT>
 __device__ __forceinline__ u32x4_t wload(const uint8_t* p) {
   if constexpr (NT) return ld_nt16(p);
   else return *(const u32x4_t*)p;
-}
-
-__device__ __forceinline__ void fp8x16_to_bf16(const u32x4_t w, bf16x8_t& f0, bf16x8_t& f1) {
-  f0 = __builtin_bit_cast(bf16x8_t, fp8x8_to_bf16(w[0], w[1]));
-  f1 = __builtin_bit_cast(bf16x8_t, fp8x8_to_bf16(w[2], w[3]));
 }
 
 // ============================================================================ decode, 16 < M <= 32

@@ -38,6 +38,23 @@ hipError_t moe_group(const int* ids, int T, int E, int k, const MoeWork& work, h
 hipError_t moe_expert_gemms(const uint16_t* x, int64_t ldx, const uint16_t* gu_w, const uint16_t* down_w, int T, int E,
                             int k, int H, int I, const MoeWork& work, hipStream_t stream);
 
+// Quantised experts (moe_wq.hip).  MOE_W_FP8: e4m3fn codes [E, N, K] with fp32 scales [E, N], H and I
+// multiples of 64.  MOE_W_W4: two 4-bit codes per byte [E, N, K / 2] with fp16 (scale, wmin) per group
+// [E, N, K / G, 2], G = 128 where K is a multiple of 128, otherwise 32.
+enum MoeWeightFormat : int { MOE_W_BF16 = 0, MOE_W_FP8 = 1, MOE_W_W4 = 2 };
+
+// moe_expert_gemms for fp8 / 4-bit experts: gu_s / down_s are the scales or group parameters
+hipError_t moe_expert_gemms_q(const uint16_t* x, int64_t ldx, const void* gu_w, const void* gu_s, const void* down_w,
+                              const void* down_s, int format, int T, int E, int k, int H, int I, const MoeWork& work,
+                              hipStream_t stream);
+
+// One grouped GEMM with no epilogue: work.y [T k, N] fp32 in sorted order, row p = x[src_tok[p]] times
+// the matrix [N, K] of the pair's expert (after moe_group; work.g is not used).  N % 16 == 0.
+hipError_t moe_grouped_gemm(const uint16_t* x, int64_t ldx, const uint16_t* w, int T, int E, int k, int N, int K,
+                            const MoeWork& work, hipStream_t stream);
+hipError_t moe_grouped_gemm_q(const uint16_t* x, int64_t ldx, const void* w, const void* s, int format, int T, int E,
+                              int k, int N, int K, const MoeWork& work, hipStream_t stream);
+
 // out[t] = residual[t] + sum_j w[t, j] * y[pos[t k + j]] (fp32, fixed j order, one bf16 rounding)
 hipError_t moe_combine(const float* w, const uint16_t* residual, int64_t ldr, uint16_t* out, int64_t ldo, int T, int k,
                        int H, const MoeWork& work, hipStream_t stream);

@@ -19,128 +19,13 @@
 // stream), MT = 4 for prefill so the stripe's weights are re-read once per 64 rows.
 // No floating-point atomics and no cross-workgroup reduction anywhere: every output element is
 // summed in one fixed order, so results are bit-identical from run to run.
+// The GEMM kernel itself is moe_gemm.h; this file instantiates it for bf16 weights (MoeBf16), the
+// fp8 and 4-bit expert instantiations are moe_wq.hip.
 #include "common.h"
 #include "moe.h"
+#include "moe_gemm.h"
 
 namespace lumen {
-
-enum MoeMode : int { MOE_LOGITS = 0, MOE_GATE_UP = 1, MOE_DOWN = 2 };
-
-struct MoeGemmArgs {
-  const uint16_t* A;      // activation rows [*, K] bf16
-  int64_t lda;
-  const uint16_t* W;      // [E, N, K] bf16 (MOE_LOGITS: [N, K])
-  int64_t w_stride;       // elements between experts
-  void* C;                // MOE_LOGITS f32 [M, N]; MOE_GATE_UP bf16 [P, N / 2]; MOE_DOWN f32 [P, N]
-  int64_t ldc;
-  const int* rowmap;      // sorted position -> row of A (nullptr: the sorted position itself)
-  const int* cnt;
-  const int* off;
-  const int* active;      // [E + 1]
-  int M, N, K, E;
-};
-
-template <int MT, int MODE>
-__global__ void __launch_bounds__(256) moe_gemm_kernel(const MoeGemmArgs a) {
-  constexpr int NWV = 4, UNR = 4, KB = 32, ROWS = MT * 16;
-  __shared__ float red[NWV][ROWS][17];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int col = lane & 15, g = lane >> 4;
-  const int n0 = blockIdx.x * 16;
-  const int N = a.N, K = a.K;
-  int e = 0, base = 0, row_begin = 0, row_end;
-  if constexpr (MODE == MOE_LOGITS) {
-    row_begin = blockIdx.y * ROWS;
-    row_end = min(a.M, row_begin + ROWS);
-  } else {
-    if ((int)blockIdx.y >= a.active[a.E]) return;   // past the non-empty experts (workgroup-uniform)
-    e = a.active[blockIdx.y];
-    base = a.off[e];
-    row_end = a.cnt[e];
-  }
-  const uint16_t* wr = a.W + (int64_t)e * a.w_stride + (int64_t)min(n0 + col, N - 1) * K + g * (KB / 4);
-  const int nblk = K / KB;
-
-  for (int rb = row_begin; rb < row_end; rb += ROWS) {
-    const uint16_t* ar[MT];
-    bool av[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      const int m = rb + t * 16 + col;
-      av[t] = m < row_end;
-      int64_t row = 0;
-      if (av[t]) row = a.rowmap != nullptr ? a.rowmap[base + m] : base + m;
-      ar[t] = a.A + row * a.lda + g * (KB / 4);
-    }
-    f32x4_t acc[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) acc[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-    auto load_a = [&](const int kk, u32x4_t (&af)[MT]) {
-#pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        af[t] = *(const u32x4_t*)(ar[t] + kk);
-        if (!av[t]) af[t] = (u32x4_t){0u, 0u, 0u, 0u};
-      }
-    };
-    auto mma_block = [&](const u32x4_t w, const u32x4_t (&af)[MT]) {
-#pragma unroll
-      for (int t = 0; t < MT; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[t]),
-                                                         __builtin_bit_cast(bf16x8_t, w), acc[t], 0, 0, 0);
-    };
-    // wave wid takes k blocks wid, wid + 4, ... (UNR at a time)
-    int s = wid;
-    for (; s + NWV * (UNR - 1) < nblk; s += NWV * UNR) {
-      u32x4_t wf[UNR];
-      u32x4_t af[UNR][MT];
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const int kk = (s + NWV * u) * KB;
-        wf[u] = *(const u32x4_t*)(wr + kk);
-        load_a(kk, af[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) mma_block(wf[u], af[u]);
-    }
-    for (; s < nblk; s += NWV) {
-      const int kk = s * KB;
-      const u32x4_t wf = *(const u32x4_t*)(wr + kk);
-      u32x4_t af[MT];
-      load_a(kk, af);
-      mma_block(wf, af);
-    }
-    // C fragment: row t * 16 + 4 g + r, column n0 + col
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[wid][t * 16 + 4 * g + r][col] = acc[t][r];
-    __syncthreads();
-    const int m = rb + tid;
-    if (tid < ROWS && m < row_end) {
-      float v[16];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) v[c] = ((red[0][tid][c] + red[1][tid][c]) + red[2][tid][c]) + red[3][tid][c];
-      if constexpr (MODE == MOE_LOGITS) {
-        float* o = (float*)a.C + (int64_t)m * a.ldc + n0;
-#pragma unroll
-        for (int c = 0; c < 16; ++c)
-          if (n0 + c < N) o[c] = v[c];
-      } else if constexpr (MODE == MOE_GATE_UP) {   // [gate 8 | up 8] -> 8 columns of silu(gate) * up
-        float o[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) o[q] = v[q] * fast_rcp(1.f + __expf(-v[q])) * v[8 + q];
-        *(u32x4_t*)((uint16_t*)a.C + (int64_t)(base + m) * a.ldc + (n0 >> 1)) = pack8(o);
-      } else {
-        f32x4_t* o = (f32x4_t*)((float*)a.C + (int64_t)(base + m) * a.ldc + n0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = (f32x4_t){v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
-      }
-    }
-    __syncthreads();   // red is rewritten by the next row block
-  }
-}
 
 // ---------------------------------------------------------------------------------------- top-k
 // One wave per token: k rounds of a wave-wide arg-max over the row's E <= 256 logits (4 per lane),
@@ -347,10 +232,10 @@ hipError_t moe_route(const uint16_t* x, int64_t ldx, const uint16_t* gate_w, int
   const dim3 block(256);
   if (T <= 32) {
     const dim3 grid((E + 15) / 16, (T + 15) / 16);
-    hipLaunchKernelGGL((moe_gemm_kernel<1, MOE_LOGITS>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL((moe_gemm_kernel<1, MOE_LOGITS, MoeBf16>), grid, block, 0, stream, a);
   } else {
     const dim3 grid((E + 15) / 16, (T + 63) / 64);
-    hipLaunchKernelGGL((moe_gemm_kernel<4, MOE_LOGITS>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL((moe_gemm_kernel<4, MOE_LOGITS, MoeBf16>), grid, block, 0, stream, a);
   }
   hipLaunchKernelGGL(moe_topk_kernel, dim3((T + 3) / 4), block, 0, stream, logits, T, E, k, norm_topk, ids, w);
   return hipGetLastError();
@@ -364,28 +249,13 @@ hipError_t moe_group(const int* ids, int T, int E, int k, const MoeWork& work, h
 
 hipError_t moe_expert_gemms(const uint16_t* x, int64_t ldx, const uint16_t* gu_w, const uint16_t* down_w, int T, int E,
                             int k, int H, int I, const MoeWork& work, hipStream_t stream) {
-  const int P = T * k;
-  const int ny = E < P ? E : P;   // at most this many experts hold a row
-  MoeGemmArgs a{};
-  a.cnt = work.cnt; a.off = work.off; a.active = work.active;
-  a.M = P; a.E = E;
-  const dim3 block(256);
-  const bool tall = P > MOE_DECODE_PAIRS;
-  // gate | up: rows gathered from x through the sorted order
-  a.A = x; a.lda = ldx; a.rowmap = work.src_tok;
-  a.W = gu_w; a.w_stride = (int64_t)2 * I * H;
-  a.C = work.g; a.ldc = I;
-  a.N = 2 * I; a.K = H;
-  if (tall) hipLaunchKernelGGL((moe_gemm_kernel<4, MOE_GATE_UP>), dim3(2 * I / 16, ny), block, 0, stream, a);
-  else hipLaunchKernelGGL((moe_gemm_kernel<1, MOE_GATE_UP>), dim3(2 * I / 16, ny), block, 0, stream, a);
-  // down: rows of g are already in sorted order
-  a.A = work.g; a.lda = I; a.rowmap = nullptr;
-  a.W = down_w; a.w_stride = (int64_t)H * I;
-  a.C = work.y; a.ldc = H;
-  a.N = H; a.K = I;
-  if (tall) hipLaunchKernelGGL((moe_gemm_kernel<4, MOE_DOWN>), dim3(H / 16, ny), block, 0, stream, a);
-  else hipLaunchKernelGGL((moe_gemm_kernel<1, MOE_DOWN>), dim3(H / 16, ny), block, 0, stream, a);
-  return hipGetLastError();
+  return moe_launch_experts<MoeBf16>(x, ldx, gu_w, nullptr, down_w, nullptr, (int64_t)2 * I * H, (int64_t)H * I, 0, 0, T, E,
+                                     k, H, I, work, stream);
+}
+
+hipError_t moe_grouped_gemm(const uint16_t* x, int64_t ldx, const uint16_t* w, int T, int E, int k, int N, int K,
+                            const MoeWork& work, hipStream_t stream) {
+  return moe_launch_grouped<MoeBf16>(x, ldx, w, nullptr, (int64_t)N * K, 0, T, E, k, N, K, work, stream);
 }
 
 hipError_t moe_combine(const float* w, const uint16_t* residual, int64_t ldr, uint16_t* out, int64_t ldo, int T, int k,

@@ -16,10 +16,12 @@ logits, top-k, ties to the lower id) -> the chosen experts' gate|up + SwiGLU and
 rows grouped by expert on the device -> weighted combine into the residual stream
 (``ops.llm.moe_mlp``, csrc/moe.hip).  No host read and launches sized from the shapes alone, so
 decode and verify steps are captured into graphs like the dense ones.  Such a decoder runs the
-unfolded layer stack at every row count; out of scope and refused with an error: quantised experts
-(``quantize_fp8`` / ``quantize_w4``), tensor / expert parallelism (``tp.world > 1``), the
-norm-folded decode chain (``fold_norms`` leaves it unfolded) and mixed dense / sparse stacks
-(``decoder_sparse_step != 1``, ``mlp_only_layers``).
+unfolded layer stack at every row count.  Quantised experts are an explicit opt-in,
+``quantize_fp8(experts=True)`` / ``quantize_w4(experts=True)``: weight-only in both formats (fp8
+or 4-bit codes into bf16 MFMAs, csrc/moe_wq.hip), the router stays in the activation dtype;
+without the opt-in the two methods refuse a MoE decoder.  Out of scope and refused with an error:
+tensor / expert parallelism (``tp.world > 1``), the norm-folded decode chain (``fold_norms`` leaves
+it unfolded) and mixed dense / sparse stacks (``decoder_sparse_step != 1``, ``mlp_only_layers``).
 
 Tensor parallelism (Megatron): QKV and gate|up are column-parallel (whole heads /
 whole 8-column GLU groups per rank), o_proj and down are row-parallel followed by
@@ -425,22 +427,42 @@ class LLM(nn.Module):
             self.fold_norms()
             self._ssq_buf(x.device)
 
+    def _quantize_experts(self, l, quant) -> None:
+        """gu_w / down_w of a sparse layer -> codes of the same leading shape and the ``gu_s`` /
+        ``down_s`` buffers, every expert's rows quantised on the [E * N, K] view."""
+        for name in ("gu", "down"):
+            w = getattr(l, name + "_w")
+            E, N, K = w.shape
+            codes, sc = quant(w.view(E * N, K))
+            setattr(l, name + "_w", nn.Parameter(codes.view(E, N, -1), requires_grad=False))
+            l.register_buffer(name + "_s", sc.view(E, N, *sc.shape[1:]), persistent=False)
+
     @torch.no_grad()
-    def quantize_fp8(self, lm_head: bool = True) -> None:
+    def quantize_fp8(self, lm_head: bool = True, experts: bool = False) -> None:
         """fp8 decoder: QKV / o / gate|up / down (and an untied lm_head) become OCP e4m3fn
         with per-output-row fp32 scales (``<name>_s`` buffers).  Decode GEMMs (<= 32 rows)
         are HBM-bound on weights and stream the fp8 weights into bf16 MFMAs (half the bytes
         per token); prefill quantises the activations per token and runs fp8 x fp8 on the
-        block-scaled matrix cores (:meth:`_f8_ok`).  Accumulation and epilogues are fp32."""
-        if self.moe:
-            raise NotImplementedError("quantize_fp8: quantised experts are not implemented for a mixture-of-experts decoder")
+        block-scaled matrix cores (:meth:`_f8_ok`).  Accumulation and epilogues are fp32.
+
+        A mixture-of-experts decoder is quantised only with ``experts=True`` (ignored by a dense
+        one): gate|up / down of every expert become e4m3fn with ``gu_s`` [E, 2I] / ``down_s``
+        [E, H], weight-only at every row count (the grouped GEMMs of csrc/moe_wq.hip; there is no
+        W8A8 sparse MLP).  The router, the embedding and the q / k norms keep their dtype."""
+        if self.moe and not experts:
+            raise NotImplementedError("quantize_fp8: a mixture-of-experts decoder is quantised only on request, "
+                                      "quantize_fp8(experts=True) (fp8 experts in the grouped GEMMs, weight-only)")
         if self.weight_dtype == "fp8":
             return
+        if self.moe and (self.cfg.hidden_size % 64 or self.cfg.moe_intermediate_size % 64):
+            raise ValueError("quantize_fp8: fp8 experts need hidden_size and moe_intermediate_size to be multiples of 64")
         for l in self.layers:
-            for name in ("qkv", "o", "gu", "down"):
+            for name in ("qkv", "o") if self.moe else ("qkv", "o", "gu", "down"):
                 w8, sc = ops.quantize_fp8_rows(getattr(l, name + "_w"))
                 setattr(l, name + "_w", nn.Parameter(w8, requires_grad=False))
                 l.register_buffer(name + "_s", sc, persistent=False)
+            if self.moe:
+                self._quantize_experts(l, ops.quantize_fp8_rows)
         if lm_head and self.lm_head is not None:
             w8, sc = ops.quantize_fp8_rows(self.lm_head)
             self.lm_head = nn.Parameter(w8, requires_grad=False)
@@ -448,27 +470,35 @@ class LLM(nn.Module):
         self.weight_dtype = "fp8"
 
     @torch.no_grad()
-    def quantize_w4(self, lm_head: bool = True) -> None:
+    def quantize_w4(self, lm_head: bool = True, experts: bool = False) -> None:
         """4-bit decoder (weight-only): QKV / o / gate|up / down (and an untied lm_head) become
         group-quantised 4-bit codes, uint8 [N, K / 2], with float16 (scale, wmin) per group of
         128 (32 where the local K is no multiple of 128) in the ``<name>_s`` buffers
         (ops.quantize_w4_rows).  Activations stay bf16 and accumulation fp32 at every row
         count (csrc/gemm_w4.hip); the embedding stays bf16.  The RMSNorm gammas are folded
         first (on any device) and ``norm_folded`` stays set, so the codes are never
-        requantised by a later fold."""
-        if self.moe:
-            raise NotImplementedError("quantize_w4: quantised experts are not implemented for a mixture-of-experts decoder")
+        requantised by a later fold.
+
+        A mixture-of-experts decoder is quantised only with ``experts=True`` (ignored by a dense
+        one): gate|up / down of every expert become codes [E, N, K / 2] with ``gu_s``
+        [E, 2I, H / G, 2] / ``down_s`` [E, H, I / G, 2] (csrc/moe_wq.hip).  It stays unfolded
+        (``norm_folded`` False); the router, the embedding and the q / k norms keep their dtype."""
+        if self.moe and not experts:
+            raise NotImplementedError("quantize_w4: a mixture-of-experts decoder is quantised only on request, "
+                                      "quantize_w4(experts=True) (4-bit experts in the grouped GEMMs)")
         if self.weight_dtype == "w4":
             return
         assert self.weight_dtype == "bf16", "quantize_w4 starts from float weights"
         self.fold_norms()
         for l in self.layers:
-            for name in ("qkv", "o", "gu", "down"):
+            for name in ("qkv", "o") if self.moe else ("qkv", "o", "gu", "down"):
                 w = getattr(l, name + "_w")
                 assert w.shape[1] % 32 == 0, f"w4: local K of {name} ({w.shape[1]}) must be a multiple of 32"
                 w4, p4 = ops.quantize_w4_rows(w)
                 setattr(l, name + "_w", nn.Parameter(w4, requires_grad=False))
                 l.register_buffer(name + "_s", p4, persistent=False)
+            if self.moe:
+                self._quantize_experts(l, ops.quantize_w4_rows)
         if lm_head and self.lm_head is not None:
             w4, p4 = ops.quantize_w4_rows(self.lm_head)
             self.lm_head = nn.Parameter(w4, requires_grad=False)
@@ -492,8 +522,9 @@ class LLM(nn.Module):
                           w_scale=getattr(l, name + "_s", None))
 
     def _f8_ok(self, T: int) -> bool:
-        """W8A8 prefill: fp8 weights, enough rows, every projection K a multiple of 128."""
-        if self.weight_dtype != "fp8" or T < _F8_MIN_ROWS:
+        """W8A8 prefill: fp8 weights, enough rows, every projection K a multiple of 128.  Never for a
+        mixture-of-experts decoder: its fp8 is weight-only (there is no W8A8 sparse MLP)."""
+        if self.weight_dtype != "fp8" or T < _F8_MIN_ROWS or self.moe:
             return False
         l = self.layers[0]
         return all(getattr(l, n + "_w").shape[1] % 128 == 0 for n in ("qkv", "o", "gu", "down"))
@@ -593,7 +624,7 @@ class LLM(nn.Module):
                 ops.rms_norm(x, l.ln2, eps, out=h)
             if self.moe:     # sparse MLP at every row count (no TP): route, grouped expert GEMMs, combine into x
                 lops.moe_mlp(h, l.router_w, l.gu_w, l.down_w, cfg.num_experts_per_tok, norm_topk=cfg.norm_topk_prob,
-                             residual=x, out=x)
+                             residual=x, out=x, gu_s=getattr(l, "gu_s", None), down_s=getattr(l, "down_s", None))
                 del qkv, att
                 continue
             g = self._lin(h, l, "gu", glu=True)

@@ -193,19 +193,21 @@ class VLM(nn.Module):
         self.invalidate_graphs()
 
     @torch.no_grad()
-    def quantize_fp8(self) -> None:
+    def quantize_fp8(self, experts: bool = False) -> None:
         """fp8 VLM: the W8A8 / fp8-weight decoder (LLM.quantize_fp8) and, for a ViT tower, the MX W8A8
-        vision chain (clip.run_blocks_mx; LUMEN_VIT_FP8=0 keeps the tower bf16)."""
-        self.llm.quantize_fp8()
+        vision chain (clip.run_blocks_mx; LUMEN_VIT_FP8=0 keeps the tower bf16).  ``experts``: the
+        opt-in a mixture-of-experts decoder needs (ignored by a dense one)."""
+        self.llm.quantize_fp8(experts=experts)
         if self.cfg.vision_arch != "fastvit" and os.environ.get("LUMEN_VIT_FP8", "1") != "0":
             self.vision.w8a8 = True
         self.invalidate_graphs()
 
     @torch.no_grad()
-    def quantize_w4(self) -> None:
+    def quantize_w4(self, experts: bool = False) -> None:
         """4-bit VLM: the group-quantised 4-bit decoder (LLM.quantize_w4); the vision tower and the
-        projector keep their precision."""
-        self.llm.quantize_w4()
+        projector keep their precision.  ``experts``: the opt-in a mixture-of-experts decoder needs
+        (ignored by a dense one)."""
+        self.llm.quantize_w4(experts=experts)
         self.invalidate_graphs()
 
     @property

@@ -15,7 +15,7 @@ import torch
 
 from .._native import hip_ops
 from ..utils.h2d import h2d
-from .moe import moe_experts, moe_mlp, moe_route, route_weights  # noqa: F401  (the sparse MLP, csrc/moe.hip)
+from .moe import moe_experts, moe_grouped_linear, moe_mlp, moe_route, route_weights  # noqa: F401  (the sparse MLP, csrc/moe.hip)
 
 KV_BLOCK = 64
 

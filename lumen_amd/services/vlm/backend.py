@@ -395,9 +395,9 @@ class MI355XVLMBackend:
             else:
                 raise ResourceNotFoundError(f"{self.resources.model_name}: model.safetensors / onnx pack missing")
             if fp8:
-                m.quantize_fp8()   # fp8 decoder + W8A8 ViT tower (config precision "fp8")
+                m.quantize_fp8(experts=True)   # fp8 decoder (a MoE one: fp8 experts) + W8A8 ViT tower (precision "fp8")
             elif w4:
-                m.quantize_w4()    # every rank quantises its own shard; the vision tower keeps its precision
+                m.quantize_w4(experts=True)    # every rank quantises its own shard; the vision tower keeps its precision
             if cached is not None:
                 shard_cache.save(m, cached[0], cached[1], cached[2], m.llm.cache_extra())
         self.model = m.eval()
