@@ -20,7 +20,7 @@ constexpr int KV_BLOCK = 64;
 struct RopeKVArgs {
   uint16_t* qkv;          // [T, ld] bf16: q heads | k heads | v heads (rotated in place)
   int64_t ld;
-  const int* pos;         // [T] positions
+  const int* pos;         // [T] positions ([3, T] with mrope, below)
   const float* cos_sin;   // [max_pos, D/2, 2] (cos, sin)
   const int64_t* slots;   // [T] cache slot = block * 64 + offset, < 0 = do not cache; null = no cache write
   uint16_t* k_cache;
@@ -32,6 +32,11 @@ struct RopeKVArgs {
   const float* q_gamma;   // [D] shared by all q heads (null = no norm; then k_gamma is null too)
   const float* k_gamma;   // [D] shared by all k heads
   float eps;
+  // multimodal RoPE (Qwen-VL prefill): pos is [3, T] axis-major (temporal, height, width) and rotary
+  // frequency i takes its (cos, sin) from row pos[axis(i)][t] of the table.  axis(i) is the two-bit
+  // code i % 32 of mrope_axes[i / 32] (0 = t, 1 = h, 2 = w); D <= 128, so 64 codes cover every i.
+  int mrope;              // 0: pos is [T] and the two words below are not read
+  uint64_t mrope_axes[2];
 };
 hipError_t rope_kv(const RopeKVArgs& a, hipStream_t stream);
 

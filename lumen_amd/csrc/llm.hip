@@ -5,7 +5,8 @@
 //    cache write (k token-major, v transposed; layouts in llm.h).  Prefill
 //    attention then reads q/k/v straight from the rotated QKV buffer.  Qwen3:
 //    every q / k head first passes through an RMSNorm over the head dim
-//    (template flag NORM of both kernel forms).
+//    (template flag NORM of both kernel forms).  Qwen-VL prefill: multimodal RoPE, three
+//    positions per token and an axis per rotary frequency (template flag MROPE of both forms).
 //  * paged_decode: flash-decoding over the paged cache.  One workgroup per
 //    (split, kv-head, sequence); the G = H / Hkv query heads sharing a kv head
 //    are the 16 MFMA columns, each wave walks its own 64-token blocks with an
@@ -43,7 +44,14 @@ namespace lumen {
 // in or wholly out, and the threads past it leave only after the butterfly.
 __device__ __forceinline__ float qk_rstd(float ssq, int D, float eps) { return rsqrtf(ssq / (float)D + eps); }
 
-template <bool NORM>
+// MROPE (llm.h): pos is [3, T] and frequency i reads the table row of the axis its two-bit code names.
+// The codes are kernel arguments, so the per-element form adds one pos load of a computed row and the
+// tile form three pos loads per thread; neither adds a load that another depends on.
+__device__ __forceinline__ int mrope_axis(const RopeKVArgs& a, int i) {
+  return (int)((i < 32 ? a.mrope_axes[0] : a.mrope_axes[1]) >> ((i & 31) * 2)) & 3;
+}
+
+template <bool NORM, bool MROPE>
 __global__ void __launch_bounds__(256) rope_kv_kernel(RopeKVArgs a, int nrot_blocks) {
   const int t = blockIdx.x;
   const int half = a.D >> 1;
@@ -59,9 +67,10 @@ __global__ void __launch_bounds__(256) rope_kv_kernel(RopeKVArgs a, int nrot_blo
     } else {
       if (!live) return;
     }
-    const int p = a.pos[t];
+    const int p = MROPE ? 0 : a.pos[t];
     const float2* cs = reinterpret_cast<const float2*>(a.cos_sin) + (int64_t)p * half;
     const int hh = idx / half, i = idx - hh * half;
+    if constexpr (MROPE) cs += (int64_t)a.pos[(int64_t)mrope_axis(a, i) * a.T + t] * half;   // the row of i's axis
     uint16_t* hp = row + hh * a.D;
     float x1 = bf2f(hp[i]), x2 = bf2f(hp[i + half]);
     if constexpr (NORM) {
@@ -109,7 +118,10 @@ __global__ void __launch_bounds__(256) rope_kv_kernel(RopeKVArgs a, int nrot_blo
 // wrote V with 2-byte stores 128 bytes apart (11 us per 8B-prefill layer at 624 tokens).
 // NORM: the 4 adjacent threads of a (token, head) each sum the D/4 squares of the values they hold;
 // two xor steps over the quad give the head's sum (a quad leaves together at the ragged last tile).
-template <int D, bool NORM>
+// MROPE: a thread's PPT consecutive frequencies are PPT two-bit codes of one argument word, shifted
+// down once; each unrolled pair picks one of the token's three table rows by a constant-shift code, so
+// only the 8-byte (cos, sin) loads become gathers (the interleaved layout changes row on every pair).
+template <int D, bool NORM, bool MROPE>
 __global__ void __launch_bounds__(256) rope_kv_tile_kernel(RopeKVArgs a) {
   constexpr int HALF = D / 2, PPT = D / 8;       // rotation pairs per thread
   __shared__ __attribute__((aligned(16))) uint16_t vt[64][D + 8];
@@ -119,7 +131,16 @@ __global__ void __launch_bounds__(256) rope_kv_tile_kernel(RopeKVArgs a) {
     const int tt = tid >> 2, c0 = (tid & 3) * PPT, t = t0 + tt;
     if (t >= a.T) return;
     uint16_t* hp = a.qkv + (int64_t)t * a.ld + hh * D;
-    const float2* cs = reinterpret_cast<const float2*>(a.cos_sin) + (int64_t)a.pos[t] * HALF + c0;
+    // (MROPE: cs is row 0 of the table and each pair adds the row of its axis)
+    const float2* cs = reinterpret_cast<const float2*>(a.cos_sin) + (int64_t)(MROPE ? 0 : a.pos[t]) * HALF + c0;
+    int row_t = 0, row_h = 0, row_w = 0;      // MROPE: first table element of the token's three rows (< 2^31)
+    uint32_t codes = 0;                       // MROPE: the axis codes of pairs c0 .. c0 + PPT - 1
+    if constexpr (MROPE) {
+      row_t = a.pos[t] * HALF;
+      row_h = a.pos[(int64_t)a.T + t] * HALF;
+      row_w = a.pos[2 * (int64_t)a.T + t] * HALF;
+      codes = (uint32_t)((c0 < 32 ? a.mrope_axes[0] : a.mrope_axes[1]) >> ((c0 & 31) * 2));
+    }
     u32x4_t raw1[PPT / 8], raw2[PPT / 8];   // NORM: the thread's values, held across the reduction
     float g1[PPT], g2[PPT];                 // NORM: gamma of each element, 16-byte loads
     float rstd = 1.f;
@@ -164,7 +185,13 @@ __global__ void __launch_bounds__(256) rope_kv_tile_kernel(RopeKVArgs a) {
       }
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const float2 c = cs[u + q];
+        float2 c;
+        if constexpr (MROPE) {
+          const uint32_t ax = (codes >> (2 * (u + q))) & 3u;
+          c = cs[(ax == 1u ? row_h : ax == 2u ? row_w : row_t) + u + q];
+        } else {
+          c = cs[u + q];
+        }
         y1[u + q] = x1[q] * c.x - x2[q] * c.y;
         y2[u + q] = x2[q] * c.x + x1[q] * c.y;
       }
@@ -233,22 +260,24 @@ hipError_t rope_kv(const RopeKVArgs& a, hipStream_t stream) {
   const bool norm = a.q_gamma != nullptr;
   // the norm's segmented butterfly needs a power-of-two D/2 that divides the wave
   if (norm && (a.k_gamma == nullptr || !(a.D == 32 || a.D == 64 || a.D == 128))) return hipErrorInvalidValue;
+  const bool mrope = a.mrope != 0;
+  if (mrope && a.D > 128) return hipErrorInvalidValue;   // two words hold 64 axis codes
   if (a.T >= 64 && (a.D == 64 || a.D == 128) && a.ld % 8 == 0) {
     const dim3 grid((a.T + 63) / 64, a.H + 2 * a.Hkv);
-    if (a.D == 128) {
-      if (norm) hipLaunchKernelGGL((rope_kv_tile_kernel<128, true>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((rope_kv_tile_kernel<128, false>), grid, dim3(256), 0, stream, a);
-    } else {
-      if (norm) hipLaunchKernelGGL((rope_kv_tile_kernel<64, true>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((rope_kv_tile_kernel<64, false>), grid, dim3(256), 0, stream, a);
-    }
+    auto tile = a.D == 128
+        ? (norm ? (mrope ? rope_kv_tile_kernel<128, true, true> : rope_kv_tile_kernel<128, true, false>)
+                : (mrope ? rope_kv_tile_kernel<128, false, true> : rope_kv_tile_kernel<128, false, false>))
+        : (norm ? (mrope ? rope_kv_tile_kernel<64, true, true> : rope_kv_tile_kernel<64, true, false>)
+                : (mrope ? rope_kv_tile_kernel<64, false, true> : rope_kv_tile_kernel<64, false, false>));
+    hipLaunchKernelGGL(tile, grid, dim3(256), 0, stream, a);
     return hipGetLastError();
   }
   const int nrot_blocks = ((a.H + a.Hkv) * (a.D / 2) + 255) / 256;
   const int v_blocks = a.slots ? (a.Hkv * a.D + 255) / 256 : 0;
   const dim3 grid(a.T, nrot_blocks + v_blocks);
-  if (norm) hipLaunchKernelGGL(rope_kv_kernel<true>, grid, dim3(256), 0, stream, a, nrot_blocks);
-  else hipLaunchKernelGGL(rope_kv_kernel<false>, grid, dim3(256), 0, stream, a, nrot_blocks);
+  auto elem = norm ? (mrope ? rope_kv_kernel<true, true> : rope_kv_kernel<true, false>)
+                   : (mrope ? rope_kv_kernel<false, true> : rope_kv_kernel<false, false>);
+  hipLaunchKernelGGL(elem, grid, dim3(256), 0, stream, a, nrot_blocks);
   return hipGetLastError();
 }
 

@@ -57,15 +57,21 @@ bool check_qk_norm(const c10::optional<at::Tensor>& qg, const c10::optional<at::
 
 // qkv [T, >= (H + 2 Hkv) D] bf16 (rotated in place); pos int32 [T]; cos_sin f32 [P, D/2, 2];
 // slots int64 [T] (optional): writes rotated k / v into the paged cache.  q_gamma / k_gamma f32 [D]
-// (optional): per-head RMSNorm of q and k before the rotation.
+// (optional): per-head RMSNorm of q and k before the rotation.  mrope_axes uint8 [D/2] on the host
+// (optional, values 0 / 1 / 2): multimodal RoPE, pos int32 [3, T] and frequency i rotated by the
+// position of axis mrope_axes[i] (ops/llm.py mrope_axes).
 void rope_kv(at::Tensor qkv, const at::Tensor& pos, const at::Tensor& cos_sin, const c10::optional<at::Tensor>& slots,
              at::Tensor k_cache, at::Tensor v_cache, int64_t H, int64_t Hkv, int64_t D,
-             const c10::optional<at::Tensor>& q_gamma, const c10::optional<at::Tensor>& k_gamma, double qk_eps) {
+             const c10::optional<at::Tensor>& q_gamma, const c10::optional<at::Tensor>& k_gamma, double qk_eps,
+             const c10::optional<at::Tensor>& mrope_axes) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1, "qkv");
   TORCH_CHECK(qkv.size(1) >= (H + 2 * Hkv) * D, "qkv: too few columns");
   TORCH_CHECK(D % 2 == 0 && D <= 256, "rope: head dim");
   const int64_t T = qkv.size(0);
-  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.numel() == T && pos.is_contiguous(), "pos int32 [T]");
+  const bool mrope = mrope_axes.has_value() && mrope_axes->defined();
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.is_contiguous(), "pos int32");
+  TORCH_CHECK(mrope || pos.numel() == T, "pos int32 [T]");
+  TORCH_CHECK(!mrope || (pos.dim() == 2 && pos.size(0) == 3 && pos.size(1) == T), "mrope: pos int32 [3, T]");
   TORCH_CHECK(cos_sin.is_cuda() && cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous() &&
               cos_sin.dim() == 3 && cos_sin.size(1) == D / 2 && cos_sin.size(2) == 2, "cos_sin f32 [P, D/2, 2]");
   lumen::RopeKVArgs a{};
@@ -80,6 +86,17 @@ void rope_kv(at::Tensor qkv, const at::Tensor& pos, const at::Tensor& cos_sin, c
   }
   a.T = (int)T; a.H = (int)H; a.Hkv = (int)Hkv; a.D = (int)D;
   if (check_qk_norm(q_gamma, k_gamma, qk_eps, D, qkv, &a.q_gamma, &a.k_gamma)) a.eps = (float)qk_eps;
+  if (mrope) {
+    TORCH_CHECK(D == 32 || D == 64 || D == 128, "mrope: head dim 32, 64 or 128");
+    TORCH_CHECK(mrope_axes->is_cpu() && mrope_axes->scalar_type() == at::kByte && mrope_axes->is_contiguous() &&
+                mrope_axes->numel() == D / 2, "mrope: axes uint8 [D/2] on the host");
+    const uint8_t* ax = mrope_axes->data_ptr<uint8_t>();
+    for (int64_t i = 0; i < D / 2; ++i) {
+      TORCH_CHECK(ax[i] <= 2, "mrope: axes are 0 (t), 1 (h) or 2 (w)");
+      a.mrope_axes[i >> 5] |= (uint64_t)ax[i] << ((i & 31) * 2);
+    }
+    a.mrope = 1;
+  }
   const at::DeviceGuard g(qkv.device());
   CHECK_HIP3(lumen::rope_kv(a, cur()));
 }
@@ -464,7 +481,8 @@ void upload_small(const at::Tensor& src, at::Tensor out) {
 TORCH_LIBRARY_FRAGMENT(lumen, m) {
   m.def("upload_small(Tensor src, Tensor(o!) out) -> ()");
   m.def("rope_kv(Tensor(a!) qkv, Tensor pos, Tensor cos_sin, Tensor? slots, Tensor(k!) k_cache, Tensor(v!) v_cache, "
-        "int H, int Hkv, int D, Tensor? q_gamma=None, Tensor? k_gamma=None, float qk_eps=0.0) -> ()");
+        "int H, int Hkv, int D, Tensor? q_gamma=None, Tensor? k_gamma=None, float qk_eps=0.0, "
+        "Tensor? mrope_axes=None) -> ()");
   m.def("paged_decode(Tensor q, Tensor(k!) k_cache, Tensor(v!) v_cache, Tensor block_table, Tensor ctx_len, "
         "Tensor(o!) out, int H, int Hkv, float scale, int nsplit, int blocks_per_split, Tensor(p!)? part_o=None, "
         "Tensor(m!)? part_ml=None, Tensor? pos=None, Tensor? cos_sin=None, Tensor? slots=None, Tensor? pf0=None, "

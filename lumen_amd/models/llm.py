@@ -1,4 +1,4 @@
-"""Llama / Qwen2 / Qwen3 / Qwen3-MoE decoder for the VLM, tensor-parallel over RCCL.
+"""Llama / Qwen2 / Qwen3 / Qwen3-MoE / Qwen-VL decoder for the VLM, tensor-parallel over RCCL.
 
 Reference: the FastVLM decoder ONNX graph (Qwen2-0.5B) driven by
 packages/lumen-vlm/src/lumen_vlm/backends/onnxrt_backend.py:161-533; the north star
@@ -22,6 +22,16 @@ or 4-bit codes into bf16 MFMAs, csrc/moe_wq.hip), the router stays in the activa
 without the opt-in the two methods refuse a MoE decoder.  Out of scope and refused with an error:
 tensor / expert parallelism (``tp.world > 1``), the norm-folded decode chain (``fold_norms`` leaves
 it unfolded) and mixed dense / sparse stacks (``decoder_sparse_step != 1``, ``mlp_only_layers``).
+
+Qwen2-VL / Qwen2.5-VL / Qwen3-VL decoders (``rope_scaling`` with ``mrope_section``): multimodal RoPE.
+Every token has three positions (temporal, height, width; ``ops.llm.mrope_positions``) and each
+rotary frequency takes its angle from one of them (``LLMConfig.mrope``, ``ops.llm.mrope_axes``).  Only
+the prefill needs the three axes (``prefill(pos3=...)``, the MROPE form of the RoPE kernels): a
+generated token is a text token whose three positions are equal, cache index + the prompt's rope
+delta, so ``decode`` / ``verify`` run the 1-D kernels at that shifted position.  The causal masks
+keep using cache indices.  Their checkpoints hold the decoder under ``model.language_model.``
+(``load_hf_state_dict(prefix=...)``).  Out of scope: the Qwen-VL vision towers, DeepStack inputs,
+video grids, tensor parallelism with ``pos3`` and the fused experts of Qwen3-VL-MoE (refused).
 
 Tensor parallelism (Megatron): QKV and gate|up are column-parallel (whole heads /
 whole 8-column GLU groups per rank), o_proj and down are row-parallel followed by
@@ -76,6 +86,12 @@ _PAGED_PREFILL_MAX_ROWS = 512
 # and was removed in r5; the MX W8A8 chain stays for the ViT tower, models/clip.py:run_blocks_mx)
 
 
+# HF model types by decoder family; the Qwen-VL ones also come as the ``text_config`` of a VLM config
+_QWEN_VL_TYPES = ("qwen2_vl", "qwen2_5_vl", "qwen3_vl", "qwen2_vl_text", "qwen2_5_vl_text", "qwen3_vl_text")
+_QWEN2_TYPES = ("qwen2", "qwen2_vl", "qwen2_5_vl", "qwen2_vl_text", "qwen2_5_vl_text")          # qkv bias
+_QWEN3_TYPES = ("qwen3", "qwen3_moe", "qwen3_vl", "qwen3_vl_text")                              # q / k norm
+
+
 @dataclass
 class LLMConfig:
     vocab_size: int = 151936
@@ -106,11 +122,30 @@ class LLMConfig:
         keys = LLMConfig.__dataclass_fields__.keys()
         return LLMConfig(**{k: v for k, v in d.items() if k in keys})
 
+    @property
+    def mrope(self) -> Optional[tuple]:
+        """``(sections, interleaved)`` of a multimodal-RoPE decoder (Qwen-VL: ``rope_scaling`` carries
+        ``mrope_section``), validated against head_dim; None for 1-D RoPE."""
+        sec = (self.rope_scaling or {}).get("mrope_section")
+        if sec is None:
+            return None
+        interleaved = bool(self.rope_scaling.get("mrope_interleaved", False))
+        lops.mrope_axes(self.head_dim, sec, interleaved)      # raises on sections that do not fit head_dim
+        return tuple(int(s) for s in sec), interleaved
+
     @staticmethod
     def from_hf(c: dict) -> "LLMConfig":
+        mt = c.get("model_type", "llama")
+        if any(t.startswith("qwen3_vl_moe") for t in (mt, (c.get("text_config") or {}).get("model_type", ""))):
+            raise ValueError("qwen3_vl_moe: its checkpoints fuse the experts' weights into one tensor per layer, "
+                             "which needs a loader of its own; not supported")
+        if c.get("text_config") and mt in _QWEN_VL_TYPES:
+            c = c["text_config"]
+            mt = c.get("model_type", mt)
         H = c["num_attention_heads"]
         hd = c.get("head_dim") or c["hidden_size"] // H
-        mt = c.get("model_type", "llama")
+        # newer HF configs carry the scaling dict, rope_theta included, as ``rope_parameters``
+        rope = c.get("rope_scaling") or c.get("rope_parameters")
         moe = {}
         if mt == "qwen3_moe":
             if c.get("decoder_sparse_step", 1) != 1:
@@ -124,11 +159,12 @@ class LLMConfig:
                        norm_topk_prob=bool(c.get("norm_topk_prob", False)))
         return LLMConfig(vocab_size=c["vocab_size"], hidden_size=c["hidden_size"], num_layers=c["num_hidden_layers"],
                          num_heads=H, num_kv_heads=c.get("num_key_value_heads", H), head_dim=hd,
-                         intermediate_size=c["intermediate_size"], rope_theta=c.get("rope_theta", 10000.0),
+                         intermediate_size=c["intermediate_size"],
+                         rope_theta=c.get("rope_theta") or (rope or {}).get("rope_theta", 10000.0),
                          rms_eps=c.get("rms_norm_eps", 1e-6), max_position=c.get("max_position_embeddings", 4096),
                          tie_word_embeddings=c.get("tie_word_embeddings", False),
-                         qkv_bias=c.get("attention_bias", mt == "qwen2"), qk_norm=mt in ("qwen3", "qwen3_moe"),
-                         rope_scaling=c.get("rope_scaling"),
+                         qkv_bias=c.get("attention_bias", mt in _QWEN2_TYPES), qk_norm=mt in _QWEN3_TYPES,
+                         rope_scaling=rope,
                          bos_token_id=c.get("bos_token_id") or 0,
                          eos_token_id=(c.get("eos_token_id")[0] if isinstance(c.get("eos_token_id"), list)
                                        else c.get("eos_token_id") or 0), **moe)
@@ -165,6 +201,16 @@ LLM_PRESETS = {
     "tiny-qwen3": LLMConfig(vocab_size=512, hidden_size=128, num_layers=2, num_heads=4, num_kv_heads=2, head_dim=64,
                             intermediate_size=256, max_position=2048, qkv_bias=False, qk_norm=True, bos_token_id=1,
                             eos_token_id=2),
+    # Qwen-VL test shapes (multimodal RoPE): the tiny shape with head_dim 64, contiguous sections, qkv
+    # bias and no q / k norm (Qwen2-VL / Qwen2.5-VL); tiny-qwen3 with interleaved sections (Qwen3-VL)
+    "tiny-qwen2vl": LLMConfig(vocab_size=512, hidden_size=128, num_layers=2, num_heads=4, num_kv_heads=2,
+                              head_dim=64, intermediate_size=256, max_position=2048, bos_token_id=1, eos_token_id=2,
+                              rope_scaling={"rope_type": "default", "mrope_section": [8, 12, 12]}),
+    "tiny-qwen3vl": LLMConfig(vocab_size=512, hidden_size=128, num_layers=2, num_heads=4, num_kv_heads=2,
+                              head_dim=64, intermediate_size=256, max_position=2048, qkv_bias=False, qk_norm=True,
+                              bos_token_id=1, eos_token_id=2,
+                              rope_scaling={"rope_type": "default", "mrope_section": [12, 10, 10],
+                                            "mrope_interleaved": True}),
     # Qwen3-MoE test shape: tiny-qwen3 with 8 experts of 64, 2 per token
     "tiny-qwen3-moe": LLMConfig(vocab_size=512, hidden_size=128, num_layers=2, num_heads=4, num_kv_heads=2,
                                 head_dim=64, intermediate_size=256, max_position=2048, qkv_bias=False, qk_norm=True,
@@ -293,7 +339,8 @@ class LLM(nn.Module):
     @torch.no_grad()
     def load_hf_state_dict(self, sd: dict, prefix: str = "model.") -> None:
         """HF Qwen2 / Qwen3 / Llama weights (``model.layers.N.self_attn.q_proj.weight`` ...), sharded for
-        this rank.  The Qwen3 ``self_attn.{q,k}_norm.weight`` must be present exactly when
+        this rank.  Qwen2-VL / Qwen2.5-VL / Qwen3-VL checkpoints keep the decoder under
+        ``prefix="model.language_model."``.  The Qwen3 ``self_attn.{q,k}_norm.weight`` must be present exactly when
         ``cfg.qk_norm`` is set: a decoder that dropped them would serve wrong tokens silently."""
         cfg, r, w = self.cfg, self.tp.rank, self.tp.world
         D = cfg.head_dim
@@ -586,8 +633,10 @@ class LLM(nn.Module):
         return (l.q_norm, l.k_norm, self.cfg.rms_eps) if l.q_norm is not None else None
 
     def _rope_kv(self, qkv, pos, l, slots, kc, vc) -> None:
-        """(q / k norm +) RoPE in place on the packed QKV rows + the paged KV-cache write of one layer."""
-        lops.rope_kv(qkv, pos, self.cos_sin, l.H, l.Hkv, self.cfg.head_dim, slots, kc, vc, qk_norm=self._qk_norm(l))
+        """(q / k norm +) RoPE in place on the packed QKV rows + the paged KV-cache write of one layer.
+        ``pos`` [3, T] (the prefill of a multimodal-RoPE decoder): the three-axis form of the kernels."""
+        lops.rope_kv(qkv, pos, self.cos_sin, l.H, l.Hkv, self.cfg.head_dim, slots, kc, vc, qk_norm=self._qk_norm(l),
+                     mrope=self.cfg.mrope if pos.dim() == 2 else None)
 
     def _layers(self, x: torch.Tensor, pos: torch.Tensor, slots: Optional[torch.Tensor], kv, attn_fn) -> torch.Tensor:
         """x [T, hidden] residual stream (updated in place); returns x."""
@@ -785,9 +834,13 @@ class LLM(nn.Module):
     # ------------------------------------------------------------------ forward passes
     @torch.no_grad()
     def prefill(self, x: torch.Tensor, kv=None, slots: Optional[torch.Tensor] = None, start_pos: int = 0,
-                prefix_blocks: Optional[torch.Tensor] = None) -> torch.Tensor:
+                prefix_blocks: Optional[torch.Tensor] = None, pos3: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One sequence: input embeddings x [T, hidden] (modified in place) at positions
         start_pos.., k/v written to ``slots``; returns last-token logits [1, V/tp] fp32.
+
+        ``pos3`` (a multimodal-RoPE decoder, ``cfg.mrope``): int32 [3, T] RoPE positions of *these*
+        rows (``lops.mrope_positions``; default: start_pos.. on all three axes).  ``start_pos`` stays
+        the rows' cache index, which the causal masks use.
 
         Chunked prefill (``start_pos`` > 0): ``prefix_blocks`` (int64, the sequence's KV
         blocks covering [0, start_pos + T)) — the chunk's queries attend the cached prefix
@@ -798,6 +851,17 @@ class LLM(nn.Module):
         self._maybe_fold(x)
         T = x.shape[0]
         pos = torch.arange(start_pos, start_pos + T, device=x.device, dtype=torch.int32)
+        if pos3 is not None:
+            if self.cfg.mrope is None:
+                raise ValueError("prefill: pos3 given to a decoder without multimodal RoPE (no mrope_section)")
+            if self.tp.enabled:
+                raise NotImplementedError("prefill: pos3 (multimodal RoPE) is not implemented under tensor "
+                                          "parallelism: the TP step messages carry no positions")
+            if tuple(pos3.shape) != (3, T):
+                raise ValueError(f"prefill: pos3 [3, {T}] expected, got {list(pos3.shape)}")
+            pos = pos3.to(device=x.device, dtype=torch.int32).contiguous()
+        elif self.cfg.mrope is not None:
+            pos = pos.expand(3, T).contiguous()
         D = self.cfg.head_dim
         S = start_pos + T
         paged = start_pos > 0 and x.is_cuda and D in lops.PAGED_PREFILL_HEAD_DIMS and \

@@ -13,6 +13,9 @@ Presets:
 * ``llava-llama3-8b`` — north-star config: CLIP ViT-L/14-336 (penultimate layer,
   576 tokens, CLS dropped) -> 2-layer GELU MLP projector -> Llama-3-8B.
 * ``tiny`` — CPU tests.
+* ``tiny-qwen2vl`` / ``tiny-qwen3vl`` — multimodal-RoPE decoders (Qwen2-VL / Qwen3-VL layouts, models/llm.py)
+  behind the same ViT tower; :meth:`VLM.rope_positions` gives a prompt's three-axis positions.  The
+  Qwen-VL vision towers themselves are not implemented.
 
 MI355X path: one fused pad/resize/normalise/patchify kernel, the ViT on the MFMA
 kernels, projector GEMMs whose second GEMM writes straight into the rows of the
@@ -149,6 +152,12 @@ VLM_PRESETS = {
     "tiny-qwen3-moe": VLMConfig(vision=VisionConfig(image_size=32, patch_size=8, width=64, layers=2, heads=2,
                                                     act="gelu"),
                                 llm=LLM_PRESETS["tiny-qwen3-moe"], image_token_id=259),
+    # multimodal-RoPE decoders behind the tiny ViT: a 4 x 4 grid of image tokens advances the position
+    # by 4, so every image moves the text after it 12 positions behind its cache index
+    "tiny-qwen2vl": VLMConfig(vision=VisionConfig(image_size=32, patch_size=8, width=64, layers=2, heads=2, act="gelu"),
+                              llm=LLM_PRESETS["tiny-qwen2vl"], image_token_id=259),
+    "tiny-qwen3vl": VLMConfig(vision=VisionConfig(image_size=32, patch_size=8, width=64, layers=2, heads=2, act="gelu"),
+                              llm=LLM_PRESETS["tiny-qwen3vl"], image_token_id=259),
     "tiny-fastvit": VLMConfig(vision=VisionConfig(image_size=64, patch_size=16, width=128, layers=0, heads=1),
                               vision_arch="fastvit", fastvit=FASTVIT_PRESETS["tiny-ln"], llm=LLM_PRESETS["tiny"],
                               image_token_id=259),
@@ -377,6 +386,19 @@ class VLM(nn.Module):
                 out.append(int(t))
         return out, starts
 
+    def rope_positions(self, expanded_ids: Sequence[int]) -> Optional[tuple]:
+        """Multimodal-RoPE positions of a prompt whose image tokens are already expanded
+        (:meth:`expand_image_tokens`) -> (int32 [3, T] on the host, rope delta); None for a 1-D RoPE
+        decoder.  Every image is the tower's square grid of image_size // patch_size tokens a side.
+        The ids alone decide the positions, so a request whose image rows all come from the prefix
+        cache (and whose image is never decoded) still has them."""
+        if self.cfg.llm.mrope is None:
+            return None
+        from ..ops.llm import mrope_positions
+
+        g = self.cfg.vision.image_size // self.cfg.vision.patch_size
+        return mrope_positions(expanded_ids, self.cfg.image_token_id, (g, g))
+
     @torch.no_grad()
     def build_prefill(self, ids: Sequence[int], images: Sequence[torch.Tensor],
                       n_images: Optional[int] = None, shard_images: bool = False) -> torch.Tensor:
@@ -538,7 +560,8 @@ def write_vlm_model(root, name: str, preset: Optional[str] = None, seed: int = 0
                                                             "eos_token": "<|im_end|>", "bos_token": None}, indent=2))
     (root / "lumen_vlm_config.json").write_text(json.dumps(cfg.to_dict(), indent=2))
     if weights is None:
-        weights = preset in ("tiny", "tiny-h8", "tiny-gqa8", "tiny-qwen3", "tiny-qwen3-moe")
+        weights = preset in ("tiny", "tiny-h8", "tiny-gqa8", "tiny-qwen3", "tiny-qwen3-moe", "tiny-qwen2vl",
+                             "tiny-qwen3vl")
     files = ["tokenizer.json", "tokenizer_config.json", "lumen_vlm_config.json"]
     if weights:
         m = VLM(cfg, dtype=torch.float32, device="cpu")

@@ -6,6 +6,7 @@ the same semantics (cache layouts in csrc/llm.h: k [NB, Hkv, 64, D], v [NB, Hkv,
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from typing import Any, NamedTuple, Optional, Sequence
@@ -67,26 +68,106 @@ def _qk_norm_args(op, qk_norm: Optional[tuple]) -> tuple:
     return q_gamma, k_gamma, float(eps)
 
 
+def mrope_axes(head_dim: int, sections: Sequence[int], interleaved: bool = False) -> torch.Tensor:
+    """Multimodal RoPE (Qwen-VL): the position axis of every rotary frequency, uint8 [head_dim / 2]
+    with 0 = temporal, 1 = height, 2 = width.  ``sections = [s_t, s_h, s_w]`` sums to head_dim / 2.
+    Contiguous layout (Qwen2-VL, Qwen2.5-VL): the first s_t frequencies are temporal, the next s_h
+    height, the rest width.  Interleaved (Qwen3-VL): frequency i is height when i % 3 == 1 and
+    i < 3 s_h, width when i % 3 == 2 and i < 3 s_w, temporal otherwise."""
+    return _mrope_axes(int(head_dim), tuple(int(s) for s in sections), bool(interleaved)).clone()
+
+
+@functools.lru_cache(maxsize=16)
+def _mrope_axes(head_dim: int, sec: tuple, interleaved: bool) -> torch.Tensor:
+    """:func:`mrope_axes`, one shared tensor per layout (a prefill asks once per layer): read-only."""
+    half = head_dim // 2
+    if len(sec) != 3:
+        raise ValueError(f"mrope: three sections (temporal, height, width), got {list(sec)}")
+    if min(sec) < 0 or sum(sec) != half:
+        raise ValueError(f"mrope: sections {list(sec)} must sum to head_dim / 2 = {half}")
+    i = torch.arange(half)
+    if interleaved:
+        ax = torch.where((i % 3 == 1) & (i < 3 * sec[1]), 1, torch.where((i % 3 == 2) & (i < 3 * sec[2]), 2, 0))
+    else:
+        ax = (i >= sec[0]).long() + (i >= sec[0] + sec[1]).long()
+    return ax.to(torch.uint8)
+
+
+def mrope_positions(ids: Sequence[int], image_token_id: int, grid_hw: tuple) -> tuple[torch.Tensor, int]:
+    """Multimodal RoPE positions of a prompt (HF ``get_rope_index``, images only) -> (int32 [3, T], delta).
+
+    ``ids`` are the *expanded* ids: every run of gh * gw ``image_token_id`` is one image whose tokens
+    form a gh x gw grid, row-major (``grid_hw = (gh, gw)``).  A text token has t = h = w = n, one more
+    than the largest position so far; an image starting at n has t = n, h = n + row, w = n + col and the
+    token after it starts at n + max(gh, gw).  ``delta = max(pos) + 1 - T`` (<= 0): generated token at
+    cache index c is a text token at position c + delta."""
+    gh, gw = int(grid_hw[0]), int(grid_hw[1])
+    N = gh * gw
+    a = np.asarray(ids, dtype=np.int64).reshape(-1)
+    T = a.shape[0]
+    pos = np.empty((3, T), np.int32)
+    n = i = 0
+    while i < T:
+        if N > 0 and a[i] == image_token_id and i + N <= T and (a[i:i + N] == image_token_id).all():
+            cell = np.arange(N)
+            pos[0, i:i + N] = n
+            pos[1, i:i + N] = n + cell // gw
+            pos[2, i:i + N] = n + cell % gw
+            n += max(gh, gw)
+            i += N
+        else:
+            pos[:, i] = n
+            n += 1
+            i += 1
+    return torch.from_numpy(pos), n - T
+
+
+def _mrope_args(op, axes: Optional[torch.Tensor], qk_norm: Optional[tuple]) -> tuple:
+    """Trailing arguments of the HIP rope_kv up to ``mrope_axes``; a library built without it is an error."""
+    if axes is None:
+        return _qk_norm_args(op, qk_norm)
+    if not any(a.name == "mrope_axes" for a in op.default._schema.arguments):
+        raise RuntimeError(f"{op.default._schema.name}: the native HIP library was built without the multimodal "
+                           "RoPE argument; rebuild it (python -m lumen_amd._build)")
+    return (*(_qk_norm_args(op, qk_norm) or (None, None, 0.0)), axes)
+
+
 def rope_kv(qkv: torch.Tensor, pos: torch.Tensor, cos_sin: torch.Tensor, H: int, Hkv: int, D: int,
             slots: Optional[torch.Tensor] = None, k_cache: Optional[torch.Tensor] = None,
-            v_cache: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None) -> None:
+            v_cache: Optional[torch.Tensor] = None, qk_norm: Optional[tuple] = None,
+            mrope: Optional[tuple] = None) -> None:
     """Rotate q and k heads of qkv [T, (H + 2Hkv) D] in place; with ``slots`` also write k / v
     of every token into the paged cache (slot = block * 64 + offset, < 0 skipped).
 
     ``qk_norm = (q_gamma [D], k_gamma [D], eps)`` (fp32, Qwen3): every q / k head vector passes
     through an RMSNorm over D before the rotation, in fp32, rounded once after the rotation;
-    v is untouched.  Head dims 32 / 64 / 128 on the GPU."""
+    v is untouched.  Head dims 32 / 64 / 128 on the GPU.
+
+    ``mrope = (sections, interleaved)`` (Qwen-VL prefill): ``pos`` is [3, T] (temporal, height,
+    width) and rotary frequency i takes its angle from the axis :func:`mrope_axes` gives it.  Without
+    it ``pos`` is [T]."""
     T = qkv.shape[0]
+    axes = None
+    if mrope is not None:
+        axes = _mrope_axes(int(D), tuple(int(s) for s in mrope[0]), bool(mrope[1]))   # raises on bad sections
+        if tuple(pos.shape) != (3, T):
+            raise ValueError(f"rope_kv: mrope needs pos [3, {T}], got {list(pos.shape)}")
+    elif pos.numel() != T:
+        raise ValueError(f"rope_kv: pos [{T}] expected, got {list(pos.shape)} (a [3, T] pos needs mrope)")
     if qkv.is_cuda:
         op = hip_ops().rope_kv
         op(qkv, pos.to(torch.int32).contiguous(), cos_sin,
            slots.to(torch.long).contiguous() if slots is not None else None,
            k_cache if k_cache is not None else qkv, v_cache if v_cache is not None else qkv,
-           int(H), int(Hkv), int(D), *_qk_norm_args(op, qk_norm))
+           int(H), int(Hkv), int(D), *_mrope_args(op, axes, qk_norm))
         return
     if T == 0:
         return
-    cs = cos_sin[pos.long()]
+    if mrope is not None:
+        # frequency i of token t: row pos[axes[i], t] of the table
+        cs = cos_sin[pos.long()[axes.long()], torch.arange(D // 2)[:, None]].transpose(0, 1)
+    else:
+        cs = cos_sin[pos.long()]
     nq = (H + Hkv) * D
     x = qkv[:, :nq].float().view(T, H + Hkv, D)
     if qk_norm is not None:

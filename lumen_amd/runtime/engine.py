@@ -121,6 +121,8 @@ class GenRequest:
     gstate: int = -1                        # guided decoding: the grammar state after ``tokens`` (host side)
     guide_slot: Optional[int] = None        # ... row of the device's state array
     guide_base: Optional[int] = None        # ... first arena row of the request's guide
+    rope_pos: Any = None                    # multimodal RoPE: int32 [3, prompt_len] positions of the prompt (host)
+    rope_delta: int = 0                     # ... RoPE position of the token at cache index c is c + rope_delta
 
     def stream(self, timeout: Optional[float] = None) -> Iterator[tuple]:
         """yields ("token", id) ... then ("done", reason) | raises the engine error."""
@@ -325,17 +327,24 @@ class LLMEngine:
             hit.tokens = 0
 
     def submit(self, prefill_args: Any, prompt_len: int, params: SamplingParams, prefix_keys=None,
-               hit: Optional[PrefixHit] = None, prompt_ids: Optional[Sequence[int]] = None) -> GenRequest:
+               hit: Optional[PrefixHit] = None, prompt_ids: Optional[Sequence[int]] = None,
+               rope_pos=None) -> GenRequest:
         """``prefix_keys``: uint64 [n, 2], key i covering prompt tokens [64 i, 64 i + 64) and chaining
         key i - 1 -- the prompt may start from cached blocks and publishes its own after prefill.
         ``hit``: the result of an earlier :meth:`match_prefix` with the same keys (the request
         takes over its id and references).  The prefill builder must return all ``prompt_len``
         rows; rows before the hit are never read.
         ``prompt_ids``: the prompt's token ids for the speculative-decoding drafter (without them
-        it sees the generated tokens only)."""
+        it sees the generated tokens only).
+        ``rope_pos``: int32 [3, prompt_len] multimodal-RoPE positions of the prompt (a decoder with
+        ``cfg.mrope``; ``VLM.rope_positions``).  Prefill chunks rotate with their columns; generated
+        tokens with cache index + delta, delta = max(rope_pos) + 1 - prompt_len."""
         try:
             if self._stop.is_set():
                 raise RuntimeError("engine stopped")
+            rope_delta = 0
+            if rope_pos is not None:
+                rope_pos, rope_delta = self._check_rope_pos(rope_pos, prompt_len, params)
             need = prompt_len + params.max_new_tokens
             if need > self.kv.capacity_tokens:
                 raise ValueError(f"request needs {need} KV tokens, cache holds {self.kv.capacity_tokens}")
@@ -361,11 +370,31 @@ class LLMEngine:
                 hit.tokens = self.kv.blocks.match(keys[:self._hit_cap(prompt_len)], hit.rid)
         r = GenRequest(rid=hit.rid, prefill_args=prefill_args, prompt_len=prompt_len, params=params,
                        t_submit=time.perf_counter(), rng=np.random.default_rng(params.seed),
-                       cached_tokens=hit.tokens, prefix_keys=keys, prompt_ids=prompt_ids)
+                       cached_tokens=hit.tokens, prefix_keys=keys, prompt_ids=prompt_ids, rope_pos=rope_pos,
+                       rope_delta=rope_delta)
         if params.guide is not None:
             r.gstate = params.guide.start
         self._waiting.put(r)
         return r
+
+    def _check_rope_pos(self, rope_pos, prompt_len: int, params: SamplingParams) -> tuple:
+        """-> (int32 [3, prompt_len] on the host, rope delta) of a request's multimodal-RoPE positions"""
+        cfg = self.llm.cfg
+        if self.sync is not None or self.llm.tp.enabled:
+            raise ValueError("rope_pos (multimodal RoPE) is not supported under tensor parallelism")
+        if cfg.mrope is None:
+            raise ValueError("rope_pos given for a decoder without multimodal RoPE")
+        p = np.asarray(rope_pos.cpu() if isinstance(rope_pos, torch.Tensor) else rope_pos)
+        if p.shape != (3, prompt_len) or not np.issubdtype(p.dtype, np.integer):
+            raise ValueError(f"rope_pos: int32 [3, {prompt_len}] expected, got {p.dtype} {list(p.shape)}")
+        if prompt_len == 0 or int(p.min()) < 0:
+            raise ValueError("rope_pos: positions must be >= 0")
+        top = int(p.max()) + 1
+        new = min(params.max_new_tokens, max(1, cfg.max_position - prompt_len))     # as submit clips it
+        if top + new > cfg.max_position:
+            raise ValueError(f"rope_pos: positions up to {top - 1} + {new} new tokens exceed max_position "
+                             f"{cfg.max_position}")
+        return torch.from_numpy(np.ascontiguousarray(p, dtype=np.int32)), top - prompt_len
 
     def close(self) -> None:
         self._stop.set()
@@ -526,8 +555,13 @@ class LLMEngine:
         spec = Sampler.spec([r]) if last else None
         if self.sync is not None:
             self.sync.send(("pchunk", r.rid, s, e, slots, tab, spec, last))
+        pos3 = {}
+        if r.rope_pos is not None:
+            if r.rope_pos.shape[1] != T:
+                raise RuntimeError(f"rope_pos covers {r.rope_pos.shape[1]} tokens, the prefill built {T} rows")
+            pos3 = {"pos3": h2d(r.rope_pos[:, s:e].contiguous(), self.device)}
         logits = self.llm.prefill(r.x[s:e], self.kv, h2d_ahead(slots, self.device), start_pos=s,
-                                  prefix_blocks=h2d_ahead(tab, self.device) if tab is not None else None)
+                                  prefix_blocks=h2d_ahead(tab, self.device) if tab is not None else None, **pos3)
         r.done = e
         self.stats["prefill_chunks"] += 1
         self.stats["prefill_tokens"] += e - s
@@ -669,12 +703,13 @@ class LLMEngine:
             return False
 
     def _step_inputs(self, reqs, ahead: int):
-        """positions / slots / block table / context lengths of the step that feeds position
-        r.ctx + ahead of every request"""
-        pos = np.array([r.ctx + ahead for r in reqs], np.int32)
+        """positions / slots / block table / context lengths of the step that feeds cache index
+        r.ctx + ahead of every request (its RoPE position: the index + the request's rope delta)"""
+        idx = np.array([r.ctx + ahead for r in reqs], np.int32)
+        pos = idx + np.array([r.rope_delta for r in reqs], np.int32)
         slots = np.concatenate([self.kv.slots(r.rid, r.ctx + ahead, 1) for r in reqs])
         bt = self.kv.block_table([r.rid for r in reqs])
-        return pos, slots, bt, pos + 1
+        return pos, slots, bt, idx + 1
 
     def _can_look_ahead(self, reqs) -> bool:
         """every request surely runs one more step after this one (no length finish, its reserved
@@ -806,7 +841,7 @@ class LLMEngine:
             n, o = 1 + len(d), b * T
             ids[o] = r.tokens[-1]
             ids[o + 1:o + n] = d
-            pos[o:o + n] = r.ctx + np.arange(n)
+            pos[o:o + n] = r.ctx + r.rope_delta + np.arange(n)
             slots[o:o + n] = self.kv.slots(r.rid, r.ctx, n)
         bt = self.kv.block_table([r.rid for r in reqs])
         sample = self._verify_sample_inputs(reqs) if smp else None

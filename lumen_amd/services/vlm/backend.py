@@ -430,6 +430,10 @@ class MI355XVLMBackend:
             log.info("VLM %s served by %d GPU engine(s)", self.resources.model_name, remote.size)
             return
         sync = None
+        if (self.tp_size > 1 or self.tp.enabled) and self._vlm_config().llm.mrope is not None:
+            # before the group starts: the TP step messages carry no positions (like guided decoding)
+            raise BackendError(f"{self.resources.model_name}: a multimodal-RoPE decoder (Qwen-VL) is not supported "
+                               "under tensor parallelism")
         if self.tp_size > 1 and not self.tp.enabled:
             from ...parallel.tp import TPServingGroup
 
@@ -643,8 +647,10 @@ class MI355XVLMBackend:
                             top_p=float(req.top_p), repetition_penalty=float(req.repetition_penalty),
                             stop_token_ids=tuple(stops), seed=req.extra.get("seed"),
                             guide=self._guide(req.extra.get("guided"), stops))
+        # a multimodal-RoPE decoder: the prompt's three-axis positions, from the expanded ids alone
+        rope = self.model.rope_positions(full)
         r = self.engine.submit((ids, img if starts else None), len(full), sp, prefix_keys=keys, hit=hit,
-                               prompt_ids=full)
+                               prompt_ids=full, rope_pos=rope[0] if rope is not None else None)
         if hit is not None:
             hit.tokens = 0      # the request owns the references now
         return r
